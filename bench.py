@@ -14,21 +14,31 @@ One step = one pass of the hot path over one batch: CorrBlock build (split-f16 o
       lookup output slabs once per iteration (one fixed-chunk all-gather each, RCCL; "strong"
       scaling).
 
-    python bench.py [--gpus N --steps K --warmup W --batch 16 --no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W --batch 16 --dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline --no-next --no-e2e]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 
 `--gpus N` always means N ranks: without a launcher (no WORLD_SIZE in the environment) and N > 1,
 bench.py starts torch.distributed.run with N processes as a child and forwards its JSON line and
 exit code; under a launcher whose WORLD_SIZE differs from N it exits non-zero.
 
-Prints ONE JSON line on rank 0 with `roofline` (the dominant kernel, the split GEMM alone --
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the
+headline: `metric`, `value` (pairs/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+config and `corrblock_frac`.  `--dump-outputs DIR` also writes what the last timed step returned to
+its caller -- rank 0's `iters` lookup outputs, kept by that step itself -- as DIR/lookup_<i>.npy
+(float32; a fixed, seeded sample of each, under 64 MB in all).  The inputs come from seeded device
+generators: the same arguments give the same inputs, so two builds compare output for output.
+
+`--full` adds everything that takes runs of its own after the timed region: `roofline` (the dominant kernel, the split GEMM alone --
 build_split16_kernel at D = 256 --
 HIP events on its launch stream inside the timed region; `window_frac` = the whole build with its
 operand pass; `traffic` = PMC HBM bytes from profiles/latest_pmc.json when its source digest
 matches this tree), `kernels` (build, pack, lookup, build_fp32) and `cpu_baseline` (SURVEY 8(d):
 the C1 shape, B = 1, build + 12 lookups on the GPU leg's first pair; the torch restatement of the
 reference's ATen ops, oracle/torch_ref.py, on all host cores and on one core, and the C oracle;
-median of 3 after a warm-up; rank 0 at N=1 only).
+median of 3 after a warm-up; rank 0 at N=1 only), the `next_rows` and `e2e` legs, and the
+multi-rank checks (`config.rank_input_checksums`; row-shard mode: `config.check_vs_unsharded`).
+`--no-cpu-baseline`, `--no-next` and `--no-e2e` drop legs of a `--full` run.
 BENCH_SINGLE_DEVICE=1 puts every rank on cuda:0 with gloo (multi-process rehearsal on one GPU).
 """
 import argparse
@@ -144,6 +154,11 @@ def parse():
     ap.add_argument("--width", type=int, default=None, help="fmap cols")
     ap.add_argument("--dim", type=int, default=256)
     ap.add_argument("--iters", type=int, default=12)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's lookup outputs (rank 0) as DIR/lookup_<i>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel and roofline figures, the other "
+                         "precisions and legs, the CPU baseline, and run the multi-rank checks")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-next", action="store_true", help="skip the SURVEY §8f next-row measurements")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end ERAFT.forward leg")
@@ -786,6 +801,59 @@ def measure_fp32_build(f1, f2, reps=5, per=3):
                     "tests/test_build_modes_gpu.py)"}
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the last timed step's lookup outputs as path/lookup_<i>.npy, float32.  An
+    output larger than its share of DUMP_BYTES (DSEC B = 16: 99.5 MB each) is sampled at sorted
+    flat indices drawn from a seeded host generator: the same elements in every run of one shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    per = min(1 << 20, DUMP_BYTES // 4 // max(1, len(outs)))
+    g = torch.Generator().manual_seed(20240229)
+    for i, t in enumerate(outs):
+        flat = t.reshape(-1)
+        if flat.numel() > per:
+            idx = torch.randint(flat.numel(), (per,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, f"lookup_{i:02d}.npy"), flat.float().cpu().numpy())
+
+
+def base_config(a, world, B, D, H, W, iters):
+    """The result line's `config`: workload, global batch, shape, parallelism."""
+    if a.mode == "batch":
+        if (H, W) == (60, 80):
+            wl = f"DSEC 480x640 CorrBlock build + {iters} lookups, warm-start, batch {B} per GPU " \
+                 f"(BASELINE configs[1]; N>1 = configs[3])"
+        elif (H, W) == (32, 32):
+            wl = f"MVSEC 256x256 crop CorrBlock build + {iters} lookups, warm-start, batch {B} per GPU " \
+                 f"(BASELINE configs[2])"
+        else:
+            wl = f"{8 * H}x{8 * W} input CorrBlock build + {iters} lookups, warm-start, batch {B} per GPU"
+        return {"workload": wl,
+                "global_batch": world * B, "fmap": [D, H, W], "levels": 4, "radius": 4,
+                "parallelism": f"dp{world} batch-sharded, no collective"}
+    return {"workload": f"1280x720 CorrBlock build + {iters} lookups, batch {B}, query rows sharded "
+                        f"over {world} GPUs (BASELINE configs[4])",
+            "global_batch": B, "fmap": [D, H, W], "levels": 4, "radius": 4,
+            "parallelism": f"query-row shard x{world}, RCCL all-gather of fmap2 + output slabs"}
+
+
+def headline(a, world, B, elapsed, mode, cfg, ideal_s):
+    """The result line of every run: pairs/s over the timed steps and the time of one step."""
+    pairs = (world * B if a.mode == "batch" else B) * a.steps
+    return {
+        "metric": METRIC, "value": round(pairs / elapsed, 2), "unit": "pairs/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak" if a.mode == "batch" else "strong",
+        "vs_baseline": None, "dtype": "fp32" if mode == "fp32" else "fp32 (f16x3 split MFMA, fp32 accumulate)",
+        "data": "synthetic (randn fmaps, coords_grid + smooth warm-start flow)",
+        "config": cfg,
+        "corrblock_frac": round(ideal_s / (elapsed / a.steps), 4),
+    }
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -861,21 +929,30 @@ def main():
     # event after its lookups
     lean = a.mode == "batch" and eraft_amd._lib.build_mode() == "split"
 
-    def step(ev=None, last=True):
+    def step(ev=None, last=True, keep=None):
         if ev is not None and not lean:
             ev[0].record(stream)
         blk = make_block()
         if ev is not None and not lean:
             ev[1].record(stream)
-        for c in coords:
-            blk(c)
+        if keep is None:
+            for c in coords:
+                blk(c)
+        else:   # --dump-outputs, the last timed step: what the caller receives stays alive
+            keep.extend(blk(c) for c in coords)
         if ev is not None and (last or not lean):
             ev[2].record(stream)
         return blk
 
+    kept = [] if a.dump_outputs else None
     with torch.no_grad():
         for _ in range(a.warmup):
             step()
+        if kept is not None:
+            # the last timed step keeps its `iters` outputs: one untimed step that does the same
+            # leaves their blocks in the caching allocator, so that step allocates from the cache
+            # like every other one and not from the device
+            step(keep=[])
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
@@ -886,7 +963,7 @@ def main():
         eraft_amd._lib.stage_event_start = not lean   # lean: the operand pass is timed after the loop
         t0 = time.perf_counter()
         for k in range(a.steps):
-            step(evs[k], last=k == a.steps - 1)
+            step(evs[k], last=k == a.steps - 1, keep=kept if k == a.steps - 1 else None)
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
@@ -895,6 +972,31 @@ def main():
         eraft_amd._lib.stage_events = None
         eraft_amd._lib.stage_event = None
         eraft_amd._lib.stage_event_start = True
+
+    if kept is not None:
+        if rank == 0:
+            dump_outputs(a.dump_outputs, kept)
+        del kept
+    if not a.full:
+        # a plain run: the headline alone, from the wall clock over the timed steps
+        for ev in evs + stages:
+            for e in ev:
+                if e is not None:
+                    e.destroy()
+        if distributed:
+            t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if single else device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = t.item()
+        flops, build_bytes, look_bytes = algorithmic(B, D, H, W, q=q_local)
+        mode = eraft_amd._lib.build_mode()
+        t_mfma, t_hbm, _ = build_floors(flops, build_bytes, mode)
+        ideal_s = max(t_mfma, t_hbm) + iters * look_bytes / (PEAK_HBM_GBS * 1e9)
+        if rank == 0:
+            print(json.dumps(headline(a, world, B, elapsed, mode, base_config(a, world, B, D, H, W, iters),
+                                      ideal_s)), flush=True)
+        if distributed:
+            dist.destroy_process_group()
+        return
 
     if lean:
         if len(stages) != a.steps:
@@ -1022,19 +1124,8 @@ def main():
         with torch.no_grad():
             kernels["fp32_step"] = measure_fp32_step(make_block, coords, B, iters,
                                                      max(t32, t_hbm) + iters * look_bytes / (PEAK_HBM_GBS * 1e9))
-    pairs = (world * B if a.mode == "batch" else B) * a.steps
+    cfg = base_config(a, world, B, D, H, W, iters)
     if a.mode == "batch":
-        if (H, W) == (60, 80):
-            wl = f"DSEC 480x640 CorrBlock build + {iters} lookups, warm-start, batch {B} per GPU " \
-                 f"(BASELINE configs[1]; N>1 = configs[3])"
-        elif (H, W) == (32, 32):
-            wl = f"MVSEC 256x256 crop CorrBlock build + {iters} lookups, warm-start, batch {B} per GPU " \
-                 f"(BASELINE configs[2])"
-        else:
-            wl = f"{8 * H}x{8 * W} input CorrBlock build + {iters} lookups, warm-start, batch {B} per GPU"
-        cfg = {"workload": wl,
-               "global_batch": world * B, "fmap": [D, H, W], "levels": 4, "radius": 4,
-               "parallelism": f"dp{world} batch-sharded, no collective"}
         if distributed:
             # every rank's own pairs: the sum of its fmap1, gathered after the timed region
             chk = torch.tensor([float(f1.double().sum())], dtype=torch.float64,
@@ -1044,10 +1135,6 @@ def main():
             cfg["rank_input_checksums"] = [float(c.item()) for c in allc]
             cfg["rank_seeds"] = [1234 + r for r in range(world)]
     else:
-        cfg = {"workload": f"1280x720 CorrBlock build + {iters} lookups, batch {B}, query rows sharded "
-                           f"over {world} GPUs (BASELINE configs[4])",
-               "global_batch": B, "fmap": [D, H, W], "levels": 4, "radius": 4,
-               "parallelism": f"query-row shard x{world}, RCCL all-gather of fmap2 + output slabs"}
         # after the timed region, on every rank: one sharded lookup (the production exchange: RCCL
         # into the persistent chunks + ecorr_rows_assemble) against the unsharded block, bitwise
         with torch.no_grad():
@@ -1056,15 +1143,8 @@ def main():
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         cfg["check_vs_unsharded"] = "bit-exact" if ok.item() == 1.0 else "DIFFERS"
         cfg["row_partition"] = row_partition(H, world)[1]
-    res = {
-        "metric": METRIC, "value": round(pairs / elapsed, 2), "unit": "pairs/s", "n_gpus": world,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak" if a.mode == "batch" else "strong",
-        "vs_baseline": None, "dtype": "fp32" if mode == "fp32" else "fp32 (f16x3 split MFMA, fp32 accumulate)",
-        "data": "synthetic (randn fmaps, coords_grid + smooth warm-start flow)",
-        "config": cfg, "roofline": roof, "kernels": kernels,
-        "corrblock_frac": round(ideal_s / (elapsed / a.steps), 4),
-    }
+    res = headline(a, world, B, elapsed, mode, cfg, ideal_s)
+    res.update(roofline=roof, kernels=kernels)
     if a.mode == "batch" and world == 1 and not a.no_next:
         with torch.no_grad():
             res["next_rows"] = {"lookup_conv1x1_relu": measure_fused_convc1(make_block(), coords, B, H, W, device),

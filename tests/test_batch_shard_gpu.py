@@ -47,7 +47,7 @@ def test_two_rank_batch_shard(launcher):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     bench = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1",
-             "--batch", str(B), "--no-next", "--no-cpu-baseline"]
+             "--batch", str(B), "--full", "--no-next", "--no-cpu-baseline"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + bench
@@ -78,7 +78,7 @@ def test_two_rank_rowshard_bench():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "rowshard", "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--no-next", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-next", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -87,3 +87,37 @@ def test_two_rank_rowshard_bench():
     assert res["n_gpus"] == 2 and res["scaling"] == "strong"
     assert res["config"]["row_partition"] == [46, 46]
     assert res["config"]["check_vs_unsharded"] == "bit-exact"
+
+
+def test_plain_run_headline_and_dump(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` prints the headline alone (no leg that takes a
+    run of its own), times exactly N steps, and `--dump-outputs DIR` writes the last step's 12 lookup
+    outputs as float32 .npy files: sampled where larger than their share (B = 2 at 60 x 80: 3.1 M
+    elements each), under 64 MB in all."""
+    import numpy as np
+    _gpu_untouched()
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["n_gpus"] == 1 and res["unit"] == "pairs/s" and res["higher_is_better"] is True
+    assert res["ms_per_step"] > 0
+    assert res["value"] == pytest.approx(2 * 3 / (res["ms_per_step"] * 3 / 1e3), rel=1e-3)
+    for leg in ("kernels", "roofline", "next_rows", "e2e", "cpu_baseline"):
+        assert leg not in res, f"a plain run measured {leg}"
+    files = sorted(p.name for p in out.iterdir())
+    assert files == [f"lookup_{i:02d}.npy" for i in range(12)]
+    total = 0
+    for name in files:
+        arr = np.load(out / name)
+        assert arr.dtype == np.float32 and arr.shape == (1 << 20,)
+        assert np.isfinite(arr).all() and arr.std() > 0
+        total += (out / name).stat().st_size
+    assert total <= 64 * 10 ** 6

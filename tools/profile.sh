@@ -3,8 +3,8 @@
 # (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE cannot share a pass).  Usage: tools/profile.sh TAG [bench args]
 cd "$GRAFT_REPO_ROOT"
 TAG=${1:-prof}; shift
-ARGS=${@:---steps 3 --warmup 1 --no-cpu-baseline --no-next}
-KT_ARGS=${KT_ARGS:---steps 20 --warmup 5 --no-cpu-baseline --no-next}
+ARGS=${@:---steps 3 --warmup 1 --full --no-cpu-baseline --no-next}
+KT_ARGS=${KT_ARGS:---steps 20 --warmup 5 --full --no-cpu-baseline --no-next}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
@@ -25,7 +25,7 @@ for cfg in "c3:--batch 64 --height 32 --width 32" "c5:--mode rowshard"; do
   j=0
   for grp in FETCH_SIZE WRITE_SIZE; do
     j=$((j+1))
-    timeout -k 10 120 rocprofv3 --pmc $grp -d $OUT/$name/pmc$j -o run --output-format csv -- python3 bench.py $cargs --steps 3 --warmup 1 --no-cpu-baseline --no-next > $OUT/$name/pmc$j.log 2>&1
+    timeout -k 10 120 rocprofv3 --pmc $grp -d $OUT/$name/pmc$j -o run --output-format csv -- python3 bench.py $cargs --steps 3 --warmup 1 --full --no-cpu-baseline --no-next > $OUT/$name/pmc$j.log 2>&1
     rc=$?
     echo "$name pmc pass $j ($grp) rc=$rc"
     if [ $rc -ne 0 ]; then tail -5 $OUT/$name/pmc$j.log; exit $rc; fi
