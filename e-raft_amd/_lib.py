@@ -14,7 +14,7 @@ import os
 import torch  # noqa: F401  (must precede the CDLL load, see above)
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libecorr.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 MAX_LEVELS = 16
 
 ECORR_OK = 0
@@ -47,6 +47,10 @@ SYMBOLS = {
     "ecorr_build_split_gemm": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (pyramid, coords, B, H, W, q_count, levels, radius, out, stream)
     "ecorr_lookup": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    # the backward (ABI 17): (grad_out, coords, B, H, W, q_count, levels, radius, grad_pyramid, stream)
+    "ecorr_lookup_backward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    # (grad_pyramid, fmap1, fmap2, B, D, H, W, q_count, levels, grad_fmap1, grad_fmap2, stream)
+    "ecorr_build_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (pyramid, coords, B, H, W, q_count, levels, radius, weight[O][C], bias, O, out, stream)
     "ecorr_lookup_conv1x1_relu": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
     # (O, C, floats*) / (weight[O][C], O, C, packed, stream) / as ecorr_lookup_conv1x1_relu, packed weight

@@ -12,9 +12,24 @@ gather-friendly layout (layout.py); corr_pyramid materializes the reference-layo
 first access (nothing on the E-RAFT path reads it).
 
 Contract differences, all loud: inputs must be fp32 HIP tensors (the reference path is fp32,
-eraft.py:104-105); the block is forward-only (E-RAFT only ever calls it under torch.no_grad(),
-test.py:80) and refuses inputs that require grad while grad mode is on; coords must match the
-build's (B, 2, H, W) exactly.
+eraft.py:104-105); by default the block is forward-only (E-RAFT only ever calls it under
+torch.no_grad(), test.py:80) and refuses inputs that require grad while grad mode is on; coords
+must match the build's (B, 2, H, W) exactly.
+
+Training (opt-in): CorrBlock(fmap1, fmap2, num_levels, radius, differentiable=True) accepts fmaps
+that require grad and gives them gradients through the build and every `corr_fn(coords)` lookup
+(ecorr_lookup_backward / ecorr_build_backward, csrc/grad.hip).  The forward runs
+the same launches, so its values are bitwise the plain block's; under torch.no_grad(), or when no
+fmap requires grad, the block is the plain block.  Autograd never carries a pyramid-sized tensor:
+the build is a Function of the fmaps returning a one-element handle, each lookup a Function of
+(handle, coords) whose backward adds its contribution into the block's single gradient pyramid
+(allocated and zeroed on the first one) and returns a zero for the handle; the build's backward
+then runs once, after all of them, turns the gradient pyramid into the two fmap gradients and
+frees it.  Deterministic (no atomics).  Contract of the differentiable block: coords are detached
+(coords.requires_grad raises; eraft.py:127 detaches them; there is no coordinate gradient), every
+pyramid level is at least 2 x 2 (the reference's samples of a 1-pixel axis are NaN), D >= 1, one
+backward per block (a second one raises), single GPU; lookup_conv1x1_relu, bilinear_sampler and
+RowShardedCorrBlock stay forward-only.
 
 Numerics: the default build sums each product as f16 lo*hi + hi*lo + hi*hi of per-pixel-scaled
 operands: within 1e-5 normwise of the reference and closer to fp64 than its fp32
@@ -59,15 +74,100 @@ def _no_grad_inputs(*ts):
                            "(as the reference harness does, test.py:80)")
 
 
-class CorrBlock:
-    """All-pairs correlation pyramid + radius-r lookup (reference: model/corr.py:12-60)."""
+class _GradState:
+    """What the backward of one differentiable block shares: the geometry, the gradient pyramid G
+    (allocated by the first lookup backward, freed by the build backward) and the consumed flag.
+    It references neither the block nor the handle, so the autograd graph holds no cycle."""
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+    def __init__(self, shape, levels, radius, numel, device):
+        self.shape, self.levels, self.radius, self.numel, self.device = shape, levels, radius, numel, device
+        self.G = None
+        self.consumed = False
+
+
+class _BuildFn(torch.autograd.Function):
+    """(fmap1, fmap2) -> one-element handle; the pyramid itself is a buffer of the block."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, state):
+        ctx.state = state
+        ctx.save_for_backward(fmap1, fmap2)
+        return torch.zeros(1, dtype=torch.float32, device=state.device)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _grad_handle):
+        st = ctx.state
+        if st.consumed:
+            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
+                               "consumed (one backward per differentiable block)")
+        st.consumed = True
+        f1, f2 = ctx.saved_tensors
+        B, D, H, W = st.shape
+        n1, n2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        G, st.G = st.G, None
+        with _lib.on_device(st.device):
+            g1 = torch.empty_like(f1) if n1 else None
+            g2 = torch.empty_like(f2) if n2 else None
+            if G is None:   # no lookup received a gradient
+                return (None if g1 is None else g1.zero_(), None if g2 is None else g2.zero_(), None)
+            _lib.check(_lib.lib().ecorr_build_backward(
+                G.data_ptr(), f1.data_ptr(), f2.data_ptr(), B, D, H, W, H * W, st.levels,
+                None if g1 is None else g1.data_ptr(), None if g2 is None else g2.data_ptr(),
+                _lib.stream_of(f1)), "CorrBlock build backward")
+        return g1, g2, None
+
+
+class _LookupFn(torch.autograd.Function):
+    """(handle, coords) -> the lookup; backward adds into the block's gradient pyramid."""
+
+    @staticmethod
+    def forward(ctx, handle, coords, state, pyramid):
+        ctx.state = state
+        ctx.save_for_backward(coords)   # versioned: an in-place change before backward raises
+        B, _, H, W = state.shape
+        K = 2 * state.radius + 1
+        cc = coords.contiguous()
+        with _lib.on_device(state.device):
+            out = torch.empty((B, state.levels * K * K, H, W), dtype=torch.float32, device=state.device)
+            _lib.check(_lib.lib().ecorr_lookup(
+                pyramid.data_ptr(), cc.data_ptr(), B, H, W, H * W, state.levels, state.radius,
+                out.data_ptr(), _lib.stream_of(cc)), "CorrBlock lookup")
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        st = ctx.state
+        if st.consumed:
+            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
+                               "consumed (one backward per differentiable block)")
+        (coords,) = ctx.saved_tensors
+        B, _, H, W = st.shape
+        go = grad_out.contiguous()
+        cc = coords.contiguous()
+        with _lib.on_device(st.device):
+            if st.G is None:
+                st.G = torch.zeros(st.numel, dtype=torch.float32, device=st.device)
+            _lib.check(_lib.lib().ecorr_lookup_backward(
+                go.data_ptr(), cc.data_ptr(), B, H, W, H * W, st.levels, st.radius, st.G.data_ptr(),
+                _lib.stream_of(go)), "CorrBlock lookup backward")
+            return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None
+
+
+class CorrBlock:
+    """All-pairs correlation pyramid + radius-r lookup (reference: model/corr.py:12-60).
+    differentiable=True (keyword only): gradients for fmap1 / fmap2 (module docstring)."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, differentiable=False):
         self.num_levels = num_levels
         self.radius = radius
         _require_device_f32("fmap1", fmap1)
         _require_device_f32("fmap2", fmap2)
-        _no_grad_inputs(fmap1, fmap2)
+        # the gradient path is live only when asked for and needed; otherwise: the plain block
+        live = bool(differentiable) and torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
+        if not live:
+            _no_grad_inputs(fmap1, fmap2)
         if fmap1.dim() != 4 or fmap1.shape != fmap2.shape:
             raise RuntimeError(f"fmap shapes {tuple(fmap1.shape)} / {tuple(fmap2.shape)} differ "
                                "or are not [B, D, H, W]")
@@ -91,6 +191,13 @@ class CorrBlock:
         self._device = fmap1.device
         Q = H * W
         self._h, self._w, self._off = _lib.layout(B * Q, H, W, num_levels)
+        if live:
+            if D == 0:
+                raise RuntimeError("differentiable CorrBlock: D = 0 feature channels (the volume is 0 / sqrt(0) = NaN)")
+            if self._h[-1] < 2 or self._w[-1] < 2:
+                raise RuntimeError(f"differentiable CorrBlock: pyramid level {num_levels - 1} is "
+                                   f"{self._h[-1]} x {self._w[-1]}; every level must be at least 2 x 2 (the "
+                                   "reference's samples of a 1-pixel axis are NaN: division by size - 1 = 0)")
         with _lib.on_device(self._device):
             if D == 0:
                 self._pyramid = torch.full((self._off[-1],), float("nan"), dtype=torch.float32, device=self._device)
@@ -105,6 +212,10 @@ class CorrBlock:
         # keeps the fmaps alive nor trusts them after an in-place change (then: the split mode)
         self._fmap_refs = (weakref.ref(fmap1), weakref.ref(fmap2), _version(fmap1), _version(fmap2))
         self._colscale = None
+        self._grad = self._handle = None
+        if live:
+            self._grad = _GradState(self._shape, num_levels, radius, self._off[-1], self._device)
+            self._handle = _BuildFn.apply(fmap1, fmap2, self._grad)
 
     @property
     def corr_pyramid(self):
@@ -120,11 +231,17 @@ class CorrBlock:
     def __call__(self, coords):
         B, _, H, W = self._shape
         _require_device_f32("coords", coords)
-        _no_grad_inputs(coords)
+        if self._grad is not None and torch.is_grad_enabled() and coords.requires_grad:
+            raise RuntimeError("differentiable CorrBlock: coords requires grad; detach it (as eraft.py:127 does), "
+                               "there is no gradient with respect to the coordinates")
+        if self._grad is None:
+            _no_grad_inputs(coords)
         if tuple(coords.shape) != (B, 2, H, W):
             raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
         if coords.device != self._device:
             raise RuntimeError("coords is on a different device than the pyramid")
+        if self._grad is not None:
+            return _LookupFn.apply(self._handle, coords, self._grad, self._pyramid)
         coords = coords.contiguous()   # the reference accepts any strides (permute + reshape)
         K = 2 * self.radius + 1
         C = self.num_levels * K * K
@@ -153,6 +270,9 @@ class CorrBlock:
         mode = mode or os.environ.get("ECORR_CONVC1", "split")
         if mode not in ("split", "presplit", "fused"):
             raise ValueError(f"mode {mode!r}: expected 'split', 'presplit' or 'fused'")
+        if self._grad is not None:
+            raise RuntimeError("eraft_amd CorrBlock.lookup_conv1x1_relu is forward-only: a differentiable block "
+                               "gives gradients through corr_fn(coords) only")
         B, _, H, W = self._shape
         _require_device_f32("coords", coords)
         _require_device_f32("weight", weight)

@@ -219,6 +219,67 @@ ECORR_EXPORT int ecorr_lookup_qmax(const float* pyramid, const float* coords, in
     return launch_lookup(P, B, (hipStream_t)stream);
 }
 
+namespace {
+
+int grad_params(float* grad_pyramid, int B, int H, int W, int q_count, int levels, PyrGeom* g, LookupGradParams* P) {
+    if (!grad_pyramid || B <= 0 || B > 65535) return ECORR_EINVAL;
+    if (!q_count_ok(H, W, q_count)) return ECORR_EINVAL;
+    const int st = pyramid_geometry((int64_t)B * q_count, H, W, levels, g);
+    if (st != ECORR_OK) return st;
+    for (int i = 0; i < levels; ++i) {
+        P->lvl[i] = grad_pyramid + g->off[i];
+        P->lh[i] = g->h[i];
+        P->lw[i] = g->w[i];
+        P->lntx[i] = g->ntx[i];
+        P->lsz[i] = g->sz[i];
+    }
+    P->q_count = q_count;
+    P->levels = levels;
+    return ECORR_OK;
+}
+
+}  // namespace
+
+ECORR_EXPORT int ecorr_lookup_backward(const float* grad_out, const float* coords, int B, int H, int W, int q_count,
+                                       int levels, int radius, float* grad_pyramid, void* stream) {
+    if (!grad_out || !coords || !grad_pyramid || B <= 0) return ECORR_EINVAL;
+    if (!q_count_ok(H, W, q_count)) return ECORR_EINVAL;
+    if (radius < 0 || radius > 32) return ECORR_ERADIUS;
+    PyrGeom g;
+    LookupGradParams P{};
+    const int st = grad_params(grad_pyramid, B, H, W, q_count, levels, &g, &P);
+    if (st != ECORR_OK) return st;
+    P.grad_out = grad_out;
+    P.coords = coords;
+    P.radius = radius;
+    P.C = levels * (2 * radius + 1) * (2 * radius + 1);
+    return launch_lookup_backward(P, B, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_build_backward(float* grad_pyramid, const float* fmap1, const float* fmap2, int B, int D, int H,
+                                      int W, int q_count, int levels, float* grad_fmap1, float* grad_fmap2,
+                                      void* stream) {
+    if (!grad_pyramid || !fmap1 || !fmap2 || B <= 0 || D <= 0) return ECORR_EINVAL;
+    PyrGeom g;
+    LookupGradParams L{};
+    const int st = grad_params(grad_pyramid, B, H, W, q_count, levels, &g, &L);
+    if (st != ECORR_OK) return st;
+    if (g.sz[0] > 0x7fffffff) return ECORR_EINVAL;
+    BuildGradParams P{};
+    P.T = grad_pyramid + g.off[0];
+    P.f1 = fmap1;
+    P.f2 = fmap2;
+    P.g1 = grad_fmap1;
+    P.g2 = grad_fmap2;
+    P.D = D;
+    P.H = H;
+    P.W = W;
+    P.q_count = q_count;
+    P.ntx = g.ntx[0];
+    P.sz = (int)g.sz[0];
+    return launch_build_backward(L, P, B, (hipStream_t)stream);
+}
+
 ECORR_EXPORT int ecorr_lookup_conv1x1_relu(const float* pyramid, const float* coords, int B, int H, int W,
                                            int q_count, int levels, int radius, const float* weight,
                                            const float* bias, int O, float* out, void* stream) {

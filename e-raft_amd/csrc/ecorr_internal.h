@@ -71,6 +71,32 @@ struct LookupParams {
 
 int launch_lookup(const LookupParams& P, int B, hipStream_t stream);
 
+// grad.hip: the backward (ecorr_lookup_backward, ecorr_build_backward).  The gradient pyramid has the
+// pyramid's storage: lvl / lh / lw / lntx / lsz as in LookupParams.
+struct LookupGradParams {
+    const float* grad_out;   // [B][C][q_count]
+    const float* coords;     // [B][2][q_count]
+    int q_count;
+    int levels, radius;
+    int C;
+    float* lvl[ECORR_MAX_LEVELS];
+    int lh[ECORR_MAX_LEVELS], lw[ECORR_MAX_LEVELS];
+    int lntx[ECORR_MAX_LEVELS];
+    int64_t lsz[ECORR_MAX_LEVELS];
+};
+struct BuildGradParams {
+    const float* T;          // the folded level 0 of the gradient pyramid: [B * q_count][sz], tiled
+    const float* f1;         // [B][D][q_count]
+    const float* f2;         // [B][D][H][W]
+    float* g1;               // [B][D][q_count] or null
+    float* g2;               // [B][D][H][W] or null
+    int D, H, W, q_count;
+    int ntx, sz;             // level 0: tiles per tile row, stored cells per query image
+};
+int launch_lookup_backward(const LookupGradParams& P, int B, hipStream_t stream);
+// the fold over L's levels, then the GEMMs whose output is non-null
+int launch_build_backward(const LookupGradParams& L, const BuildGradParams& P, int B, hipStream_t stream);
+
 int launch_lookup_conv(const LookupParams& P, int B, const float* wt, const float* bias, int O, float* out,
                        hipStream_t stream, bool packed);
 int64_t conv1x1_packed_floats(int O, int C);

@@ -185,14 +185,20 @@ class ERAFT(nn.Module):
     {'standard', 'warm_start'}; n_first_channels = voxel bins.  fuse_motion_corr=True replaces
     `corr_fn(coords1)` + BasicMotionEncoder's `relu(convc1(corr))` with the HIP lookup + convc1
     (CorrBlock.lookup_conv1x1_relu; its ECORR_CONVC1 mode); hip_upsample=True runs upsample_flow as
-    the one-pass HIP kernel (eraft_amd.upsample_flow).  The defaults keep the
-    reference's call pattern exactly."""
+    the one-pass HIP kernel (eraft_amd.upsample_flow).  differentiable_corr=True
+    builds the CorrBlock with differentiable=True, so a loss on the predictions trains fnet (not with
+    fuse_motion_corr).  The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
     corr_radius = 4
 
-    def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False):
+    def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
+                 differentiable_corr=False):
         super().__init__()
+        if differentiable_corr and fuse_motion_corr:
+            raise ValueError("differentiable_corr=True cannot be combined with fuse_motion_corr=True: the fused "
+                             "lookup + convc1 is forward-only")
+        self.differentiable_corr = differentiable_corr
         self.fuse_motion_corr = fuse_motion_corr
         self.hip_upsample = hip_upsample
         self.image_padder = ImagePadder(min_size=32)
@@ -206,6 +212,12 @@ class ERAFT(nn.Module):
         self.cnet = BasicEncoder(output_dim=self.hidden_dim + self.context_dim, norm_fn="batch",
                                  dropout=0, n_first_channels=n_first_channels)
         self.update_block = BasicUpdateBlock(self.hidden_dim, self.corr_levels, self.corr_radius)
+
+    def freeze_bn(self):
+        """Keep every BatchNorm2d on its running statistics while the rest trains (eraft.py:60-63)."""
+        for mod in self.modules():
+            if isinstance(mod, nn.BatchNorm2d):
+                mod.eval()
 
     def initialize_flow(self, img):
         N, _, H, W = img.shape
@@ -226,8 +238,11 @@ class ERAFT(nn.Module):
         image1 = self.image_padder.pad(image1).contiguous()
         image2 = self.image_padder.pad(image2).contiguous()
         fmap1, fmap2 = self.fnet([image1, image2])
+        # differentiable_corr: gradients reach fnet through the HIP backward (corr.py); the keyword
+        # is passed only then, so a reference-signature CorrBlock can stand in otherwise
         corr_fn = CorrBlock(fmap1.float().contiguous(), fmap2.float().contiguous(),
-                            num_levels=self.corr_levels, radius=self.corr_radius)
+                            num_levels=self.corr_levels, radius=self.corr_radius,
+                            **({"differentiable": True} if self.differentiable_corr else {}))
         net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)
         coords0, coords1 = self.initialize_flow(image1)

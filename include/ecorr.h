@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define ECORR_ABI_VERSION 16
+#define ECORR_ABI_VERSION 17
 #define ECORR_MAX_LEVELS 16
 #define ECORR_TILE_H 4
 #define ECORR_TILE_W 8
@@ -105,6 +105,26 @@ int ecorr_build_split_gemm(int B, int D, int H, int W, int q_count, int levels, 
  * Replaces: CorrBlock.__call__ (corr.py:29-50) incl. bilinear_sampler (utils.py:7-21). */
 int ecorr_lookup(const float* pyramid, const float* coords, int B, int H, int W, int q_count,
                  int levels, int radius, float* out, void* stream);
+
+/* ---- The backward (ABI 17): gradients of a loss through ecorr_lookup and ecorr_build, coordinates detached ----
+ * Deterministic: a query row's gradient images are owned by one workgroup per launch and summed in
+ * a fixed order; there are no float atomics, so equal inputs give bitwise equal gradients. */
+
+/* dL/d(pyramid) += one lookup's contribution.  grad_pyramid: ecorr_pyramid_layout(B*q_count, ...) floats in the
+ * pyramid's own storage, zeroed by the caller before the block's first call.  grad_out float[B][levels*(2r+1)^2][q_count].
+ * The pixels that receive gradient are exactly the in-range corners the forward read (same coordinate
+ * arithmetic, same float in-range test: NaN, +-inf and huge coordinates add nothing).  Calls on one
+ * grad_pyramid must be stream-ordered.  B <= 65535.
+ * Same argument validation and error codes as ecorr_lookup.  Replaces: autograd of corr.py:29-50 / utils.py:7-21. */
+int ecorr_lookup_backward(const float* grad_out, const float* coords, int B, int H, int W, int q_count,
+                          int levels, int radius, float* grad_pyramid, void* stream);
+/* Consumes grad_pyramid (level 0 is overwritten by the fold of levels 1.. onto it: the backward of the
+ * 2x2 floor-mode average pools).  grad_fmap1 float[B][D][q_count] (the query slab),
+ * grad_fmap2 float[B][D][H][W] = this slab's contribution (the whole gradient when q_count = H*W); either may be NULL.
+ * fp32 matrix cores, fp32 accumulation, no workspace.
+ * Replaces: autograd of corr.py:13-27,52-60. */
+int ecorr_build_backward(float* grad_pyramid, const float* fmap1, const float* fmap2, int B, int D, int H, int W,
+                         int q_count, int levels, float* grad_fmap1, float* grad_fmap2, void* stream);
 
 /* ecorr_lookup + per-query partial maxima for ecorr_conv1x1_relu_split (ABI 15): qmax
  * float[B][3*levels][q_count], max over its 3*levels entries of query p = max_c |out[b][c][p]|
