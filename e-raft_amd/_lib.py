@@ -149,6 +149,21 @@ def check(status: int, what: str):
     raise RuntimeError(msg)
 
 
+def _require_device_f32(name, t):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{name} is on {t.device}: eraft_amd runs only on HIP devices (no CPU path)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 (got {t.dtype})")
+
+
+def _no_grad_inputs(*ts):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise RuntimeError("eraft_amd CorrBlock is forward-only; call it under torch.no_grad() "
+                           "(as the reference harness does, test.py:80)")
+
+
 def layout(rows: int, H: int, W: int, levels: int):
     """(h[], w[], off[]) of the pyramid; raises like avg_pool2d on a 0-pixel level."""
     h = (_i * levels)()
@@ -273,3 +288,76 @@ def packed_conv1x1_weight(weight, O, C, kind, st, cache):
         check(lib().ecorr_conv1x1_pack(wt.data_ptr(), O, C, packed.data_ptr(), st), "convc1 weight pack")
     cache[key] = (weight, (weight.data_ptr(), version), packed)
     return packed
+
+
+def convc1_mode(mode, presplit):
+    """The convc1 mode of a lookup_conv1x1_relu call: `mode`, else env ECORR_CONVC1, else "split";
+    presplit: whether the block has that mode."""
+    mode = mode or os.environ.get("ECORR_CONVC1", "split")
+    if mode not in ("split", "fused") and (mode != "presplit" or not presplit):
+        raise ValueError(f"mode {mode!r}: expected 'split'" + (", 'presplit'" if presplit else "") + " or 'fused'")
+    return mode
+
+
+def lookup_conv1x1_relu(pyramid, coords, shape, q_count, levels, radius, weight, bias, mode, alloc_out, cache, what,
+                        column_scale=None):
+    """relu(conv1x1(lookup(coords), weight, bias)) for the q_count queries of one block (CorrBlock: all
+    H * W; RowShardedCorrBlock: its rows): the body of both classes' lookup_conv1x1_relu.
+    coords: contiguous [B][2][q_count], checked by the caller; shape = (B, H, W) of the build;
+    alloc_out(O) -> the fp32 tensor of B * O * q_count elements to write (returned); cache: the
+    block's packed-weight cache; what: the class name for error texts.
+    mode: what convc1_mode returned (the callers resolve it before their coords checks).
+    column_scale (mode "presplit"): stream -> the presplit column exponents, or None when the block
+    cannot give them (then, as for another radius or more levels: "split")."""
+    B, H, W = shape
+    dev = pyramid.device
+    _require_device_f32("weight", weight)
+    _no_grad_inputs(weight, *(() if bias is None else (bias,)))
+    if weight.device != dev or (bias is not None and bias.device != dev):
+        raise RuntimeError("weight / bias are on a different device than the pyramid")
+    K = 2 * radius + 1
+    C = levels * K * K
+    O = weight.shape[0]
+    if weight.numel() != O * C:
+        raise RuntimeError(f"weight {tuple(weight.shape)} does not map {C} correlation channels")
+    if bias is not None:
+        _require_device_f32("bias", bias)
+        if bias.numel() != O:
+            raise RuntimeError(f"bias has {bias.numel()} elements, expected {O}")
+        bias = bias.contiguous()
+    if mode == "fused" and (O <= 0 or O % 64 != 0):
+        raise RuntimeError(f"{O} output channels: the fused kernel needs a positive multiple of 64")
+    bptr = None if bias is None else bias.data_ptr()
+    with on_device(dev):
+        out = alloc_out(O)
+        st = stream_of(out)
+        if mode == "presplit":
+            scale = column_scale(st) if radius == 4 and levels <= 4 else None
+            if scale is None:
+                mode = "split"
+        wt = packed_conv1x1_weight(weight, O, C, mode, st, cache)   # once per block
+        if mode == "presplit":
+            nbytes = ctypes.c_int64()
+            check(lib().ecorr_presplit_size(B, levels, q_count, ctypes.byref(nbytes)), f"{what} presplit size")
+            corr = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            check(lib().ecorr_lookup_presplit(
+                pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, scale.data_ptr(),
+                corr.data_ptr(), st), f"{what} lookup (presplit convc1)")
+            check(lib().ecorr_conv1x1_relu_presplit(
+                corr.data_ptr(), B, levels, q_count, scale.data_ptr(), wt.data_ptr(), bptr, O, out.data_ptr(), st),
+                f"{what} lookup+conv1x1+relu (presplit)")
+        elif mode == "split":
+            G = 3 * levels
+            corr = torch.empty((B, C, q_count), dtype=torch.float32, device=dev)
+            qmax = torch.empty((B, G, q_count), dtype=torch.float32, device=dev)
+            check(lib().ecorr_lookup_qmax(
+                pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, corr.data_ptr(),
+                qmax.data_ptr(), st), f"{what} lookup (split convc1)")
+            check(lib().ecorr_conv1x1_relu_split(
+                corr.data_ptr(), B, C, q_count, qmax.data_ptr(), G, wt.data_ptr(), bptr, O, out.data_ptr(), st),
+                f"{what} lookup+conv1x1+relu (split)")
+        else:
+            check(lib().ecorr_lookup_conv1x1_relu_packed(
+                pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, wt.data_ptr(), bptr, O,
+                out.data_ptr(), st), f"{what} lookup+conv1x1+relu")
+    return out

@@ -42,23 +42,13 @@ corr_pyramid is a materialized COPY in the reference layout: 4 levels of B*H*W q
 (1.96 GB at DSEC B=16, the whole pyramid again), made on first access and cached on the block.
 Nothing on the E-RAFT path reads it; access it only for inspection or tests.
 """
-import ctypes
-import os
 import weakref
 
 import torch
 
 from . import _lib
+from ._lib import _no_grad_inputs, _require_device_f32
 from .layout import formats, untile
-
-
-def _require_device_f32(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.device.type != "cuda":
-        raise RuntimeError(f"{name} is on {t.device}: eraft_amd runs only on HIP devices (no CPU path)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32 (got {t.dtype})")
 
 
 def _version(t):
@@ -66,12 +56,6 @@ def _version(t):
         return t._version
     except RuntimeError:   # inference tensor: no version counter (and no in-place updates)
         return -1
-
-
-def _no_grad_inputs(*ts):
-    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
-        raise RuntimeError("eraft_amd CorrBlock is forward-only; call it under torch.no_grad() "
-                           "(as the reference harness does, test.py:80)")
 
 
 class _GradState:
@@ -267,70 +251,21 @@ class CorrBlock:
                    measured no faster than "split" (DESIGN.md §3.3);
           "fused"  ecorr_lookup_conv1x1_relu_packed: one kernel, the lookup tile never leaves the
                    CU, an exact c-ordered fp32 MFMA sum (radius 4, num_levels <= 4, O a multiple of 64)."""
-        mode = mode or os.environ.get("ECORR_CONVC1", "split")
-        if mode not in ("split", "presplit", "fused"):
-            raise ValueError(f"mode {mode!r}: expected 'split', 'presplit' or 'fused'")
+        mode = _lib.convc1_mode(mode, presplit=True)
         if self._grad is not None:
             raise RuntimeError("eraft_amd CorrBlock.lookup_conv1x1_relu is forward-only: a differentiable block "
                                "gives gradients through corr_fn(coords) only")
         B, _, H, W = self._shape
         _require_device_f32("coords", coords)
-        _require_device_f32("weight", weight)
-        _no_grad_inputs(coords, weight, *(() if bias is None else (bias,)))
+        _no_grad_inputs(coords)
         if tuple(coords.shape) != (B, 2, H, W):
             raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
-        if any(t.device != self._device for t in (coords, weight, *(() if bias is None else (bias,)))):
-            raise RuntimeError("coords / weight / bias are on a different device than the pyramid")
-        K = 2 * self.radius + 1
-        C = self.num_levels * K * K
-        O = weight.shape[0]
-        if weight.numel() != O * C:
-            raise RuntimeError(f"weight {tuple(weight.shape)} does not map {C} correlation channels")
-        if bias is not None:
-            _require_device_f32("bias", bias)
-            if bias.numel() != O:
-                raise RuntimeError(f"bias has {bias.numel()} elements, expected {O}")
-            bias = bias.contiguous()
-        if mode == "fused" and (O <= 0 or O % 64 != 0):
-            raise RuntimeError(f"{O} output channels: the fused kernel needs a positive multiple of 64")
-        coords = coords.contiguous()
-        bptr = None if bias is None else bias.data_ptr()
-        with _lib.on_device(self._device):
-            out = torch.empty((B, O, H, W), dtype=torch.float32, device=self._device)
-            st = _lib.stream_of(coords)
-            if mode == "presplit":
-                scale = self._column_scale(st) if self.radius == 4 and self.num_levels <= 4 else None
-                if scale is None:
-                    mode = "split"
-            if mode == "presplit":
-                wt = _lib.packed_conv1x1_weight(weight, O, C, "presplit", st, self._wcache)   # once per block
-                nbytes = ctypes.c_int64()
-                _lib.check(_lib.lib().ecorr_presplit_size(B, self.num_levels, H * W, ctypes.byref(nbytes)),
-                           "CorrBlock presplit size")
-                corr = torch.empty(nbytes.value, dtype=torch.uint8, device=self._device)
-                _lib.check(_lib.lib().ecorr_lookup_presplit(
-                    self._pyramid.data_ptr(), coords.data_ptr(), B, H, W, H * W, self.num_levels, self.radius,
-                    scale.data_ptr(), corr.data_ptr(), st), "CorrBlock lookup (presplit convc1)")
-                _lib.check(_lib.lib().ecorr_conv1x1_relu_presplit(
-                    corr.data_ptr(), B, self.num_levels, H * W, scale.data_ptr(), wt.data_ptr(), bptr, O,
-                    out.data_ptr(), st), "CorrBlock lookup+conv1x1+relu (presplit)")
-            elif mode == "split":
-                wt = _lib.packed_conv1x1_weight(weight, O, C, "split", st, self._wcache)   # once per block
-                G = 3 * self.num_levels
-                corr = torch.empty((B, C, H, W), dtype=torch.float32, device=self._device)
-                qmax = torch.empty((B, G, H * W), dtype=torch.float32, device=self._device)
-                _lib.check(_lib.lib().ecorr_lookup_qmax(
-                    self._pyramid.data_ptr(), coords.data_ptr(), B, H, W, H * W, self.num_levels, self.radius,
-                    corr.data_ptr(), qmax.data_ptr(), st), "CorrBlock lookup (split convc1)")
-                _lib.check(_lib.lib().ecorr_conv1x1_relu_split(
-                    corr.data_ptr(), B, C, H * W, qmax.data_ptr(), G, wt.data_ptr(), bptr, O, out.data_ptr(), st),
-                    "CorrBlock lookup+conv1x1+relu (split)")
-            else:
-                wt = _lib.packed_conv1x1_weight(weight, O, C, "fused", st, self._wcache)   # once per block
-                _lib.check(_lib.lib().ecorr_lookup_conv1x1_relu_packed(
-                    self._pyramid.data_ptr(), coords.data_ptr(), B, H, W, H * W, self.num_levels,
-                    self.radius, wt.data_ptr(), bptr, O, out.data_ptr(), st), "CorrBlock lookup+conv1x1+relu")
-        return out
+        if coords.device != self._device:
+            raise RuntimeError("coords is on a different device than the pyramid")
+        return _lib.lookup_conv1x1_relu(
+            self._pyramid, coords.contiguous(), (B, H, W), H * W, self.num_levels, self.radius, weight, bias, mode,
+            lambda O: torch.empty((B, O, H, W), dtype=torch.float32, device=self._device), self._wcache, "CorrBlock",
+            column_scale=self._column_scale)
 
     def _column_scale(self, st):
         """int[B*H*W + B]: the presplit column exponents (ecorr_split_column_scale), once per block;

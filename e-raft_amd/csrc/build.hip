@@ -6,11 +6,18 @@
 //   level{i+1} = (((x00 + x01) + x10) + x11) / 4 over 2x2 floor-mode windows of level i,
 // stored in the tiled pyramid layout of include/ecorr.h (4 x 8-float tiles per query image).
 //
-// Two GEMMs, one result contract (include/ecorr.h):
+// Two build modes, one result contract (include/ecorr.h), four GEMM kernels (launch_build):
 //   split (ecorr_build_split, default): pack_both_kernel splits every fp32 operand into
-//     per-pixel-scaled f16 hi + lo halves, written as 8-KB panels in MFMA-fragment order;
-//     build_split_kernel sums lo*hi + hi*lo + hi*hi per product on v_mfma_f32_32x32x16_f16.
-//   fp32 (ecorr_build): build_kernel on v_mfma_f32_32x32x2_f32, an exact k-ordered fmaf chain.
+//     per-pixel-scaled f16 hi + lo halves, written as operand panels in MFMA-fragment order; the
+//     GEMM sums lo*hi + hi*lo + hi*hi per product:
+//       build_split16_kernel  16 K chunks (D = 241 .. 256: the E-RAFT feature width), on
+//                             v_mfma_f32_16x16x32_f16 with its own panel layout;
+//       build_split_kernel    every other D, on v_mfma_f32_32x32x16_f16, a rolled K loop.
+//   fp32 (ecorr_build): v_mfma_f32_32x32x2_f32, an exact k-ordered fmaf chain:
+//       build_f32_kernel      D = 256 with W a multiple of 4, fmap2 16-byte aligned and 31-bit
+//                             operand offsets: 256 x 128 block tile;
+//       build_kernel          everything else: 128 x 128 block tile (16-byte loads and LDS-DMA
+//                             staging where alignment and the offsets allow).
 // Pooling is bit-exact given the same level 0 in both; per-element accumulation order does not
 // depend on the tiling, so query-slab (row-sharded) builds are bitwise the whole build's rows.
 //
@@ -158,9 +165,7 @@ __device__ __forceinline__ float* level_px(const BuildParams& P, int L, int64_t 
 // ============================================================================================
 constexpr int SQ = 256;                     // queries per split tile
 constexpr int SCHUNK = PANEL;               // LDS bytes per K chunk (the target panel)
-constexpr int SDT = 4;                      // target panel: chunks ahead = LDS buffers (NK > 0 loop)
-constexpr int SDQ = 3;                      // query fragments: chunks ahead = register sets (NK > 0 loop)
-constexpr int SNBUF = SDT;
+constexpr int SNBUF = 4;                    // LDS buffers of the target panel's chunk ring
 constexpr int SCOPIES = SCHUNK / 1024 / 4;  // LDS-DMA copies per wave per chunk (2)
 constexpr int QLOADS = 4;                   // query fragment loads per wave per chunk (hi, lo x 2 rows)
 constexpr int SLDS = 4 * 4 * 32 * 144;      // LDS bytes: the epilogue's transpose regions (> the K loop's)
@@ -181,29 +186,6 @@ __host__ __device__ __forceinline__ void split_target(int p, bool band, int& y, 
         x = 8 * (p >> 5) + (p & 7);
     }
 }
-
-// VMEM instructions a wave has issued after t(j) when the NK > 0 loop's advance(j) waits for it
-// (chunk j - 1, before its own t issue): the issue order of build_split_kernel replayed at compile
-// time (t = SCOPIES LDS-DMA pieces, q = QLOADS fragment loads; q(k) exists for k < nk).
-constexpr int split_vm_after(int j, int nk) {
-    int n = 0;
-    bool seen = false;
-    for (int k = 0; k < SDT; ++k) {   // prologue: t(k) q(k)
-        if (seen) n += SCOPIES;
-        if (k == j) seen = true;
-        if (k < SDQ && k < nk && seen) n += QLOADS;
-    }
-    for (int c = 0; c <= j - 2; ++c) {   // chunk c: t(c + SDT), q(c + SDQ)
-        if (seen) n += SCOPIES;
-        if (c + SDT == j) seen = true;
-        if (c + SDQ < nk && seen) n += QLOADS;
-    }
-    return n;
-}
-static_assert(SDT != 4 || SDQ != 3 ||
-                  (split_vm_after(0, 16) == 18 && split_vm_after(5, 16) == 16 && split_vm_after(16, 16) == 8),
-              "split loop wait counts (hand-checked for SDT 4, SDQ 3)");
-static_assert(split_vm_after(0, 16) < 41, "wait_vm_n range");
 
 // wait_vm<n> for an n that is a constant once the loop around the call is unrolled
 template <bool LGKM0, int N = 40>
@@ -440,10 +422,7 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
     }
 }
 
-// NK: K chunks known at compile time (16: D = 256, the E-RAFT feature width) -- the K loop is then
-// fully unrolled, which lets hipcc count the in-flight query loads exactly (in the rolled loop it
-// drains them at the loop header); 0 = any D.
-template <bool MUL, int NK>
+template <bool MUL>
 __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
     // ALL LDS in this one array: a second __shared__ object can make hipcc wait vmcnt(0) before
     // every ds_read while a buffer_load ... lds is in flight (cdna_hip_programming.md trap 4(a))
@@ -476,8 +455,8 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
     };
 
     // ---- operand panels of this tile: two query panels (adjacent tiles of pk1), one target panel
-    const int dc = (P.D + 15) / 16, nk = NK ? NK : dc;
-    const int64_t pstride = (int64_t)dc * PANEL;   // bytes of one 128-pixel tile's panels
+    const int nk = (P.D + 15) / 16;   // K chunks
+    const int64_t pstride = (int64_t)nk * PANEL;   // bytes of one 128-pixel tile's panels
     const int qp = 2 * qt;
     const int nqp = min(2, P.n_mt - qp);
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
@@ -578,50 +557,6 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
         PHASE;
     };
 
-    if constexpr (NK > 0) {
-        // D known at compile time: the target panel SDT chunks ahead (SDT LDS buffers), the query
-        // fragments SDQ chunks ahead in SDQ register sets.  VMEM issue order per wave: prologue
-        // t(0) q(0) t(1) q(1) ... t(SDT - 1), then chunk c issues t(c + SDT) in advance(c + 1) and
-        // q(c + SDQ) at its end; advance(j)'s wait count is split_vm_after(j) (loads past the last
-        // chunk are not issued: hipcc deletes loads whose registers are never read).
-        TFrags f[2];
-        QFrags qs[SDQ];
-        auto advance_n = [&](int j) {
-            PHASE;
-            wait_vm_n<true>(split_vm_after(j, NK));
-            __builtin_amdgcn_s_barrier();
-            PHASE;
-            issue(j + SDT - 1);
-            PHASE;
-        };
-#pragma unroll
-        for (int k = 0; k < SDT; ++k) {
-            issue(k);
-            PHASE;
-            if (k < SDQ) load_q(k, qs[k]);
-            PHASE;
-        }
-        wait_vm_n<true>(split_vm_after(0, NK));   // t(0) landed
-        __builtin_amdgcn_s_barrier();
-        PHASE;
-        read_lo(0, f[0]);
-        read_hi(0, f[0]);
-        PHASE;
-#pragma unroll
-        for (int kc = 0; kc < NK; ++kc) {
-            mfma_lohi(f[kc & 1], qs[kc % SDQ]);
-            PHASE;
-            advance_n(kc + 1);
-            if (kc == NK - 1) load_exponents();   // after the last static wait
-            read_lo(kc + 1, f[(kc + 1) & 1]);
-            PHASE;
-            mfma_rest(f[kc & 1], qs[kc % SDQ]);
-            PHASE;
-            read_hi(kc + 1, f[(kc + 1) & 1]);
-            if (kc + SDQ < NK) load_q(kc + SDQ, qs[kc % SDQ]);
-            PHASE;
-        }
-    } else {
     TFrags fa, fb;
     QFrags qa, qb;
     issue(0);
@@ -640,7 +575,7 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
     PHASE;
     load_q(1, qb);
     PHASE;
-#pragma unroll NK ? NK : 1
+#pragma unroll 1
     for (int kc = 0; kc < nk; kc += 2) {
         mfma_lohi(fa, qa);
         PHASE;
@@ -664,9 +599,8 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
         load_q(kc + 3, qb);
         PHASE;
     }
-    }
 #undef PHASE
-    if constexpr (NK == 0) load_exponents();
+    load_exponents();
     wait_vm<0, true>();             // the exponents and the trailing zero chunks have landed, this wave's reads are done ...
     exq[tid] = eq;
     if (tid < 128) {
@@ -1145,7 +1079,9 @@ constexpr int FDT = 3;    // target chunks ahead (LDS buffers)
 constexpr int FDQ = 2;    // query chunks ahead (register sets)
 constexpr int FQL = 16;   // query dword loads per wave and chunk (2 groups x 8 k-steps)
 
-// VMEM instructions issued after t(j) when advance(j) waits for it (see split_vm_after)
+// VMEM instructions a wave has issued after t(j) when advance(j) waits for it (chunk j - 1, before its
+// own t issue): the kernel's issue order replayed at compile time (t = SCOPIES LDS-DMA pieces, q = FQL
+// query loads; q(k) exists for k < nk)
 constexpr int f32_vm_after(int j, int nk) {
     int n = 0;
     bool seen = false;
@@ -1947,8 +1883,8 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
             if (P.scale_is_mul) hipLaunchKernelGGL((build_split16_kernel<true>), grid, dim3(256), 0, stream, P);
             else hipLaunchKernelGGL((build_split16_kernel<false>), grid, dim3(256), 0, stream, P);
         } else {
-            if (P.scale_is_mul) hipLaunchKernelGGL((build_split_kernel<true, 0>), grid, dim3(256), 0, stream, P);
-            else hipLaunchKernelGGL((build_split_kernel<false, 0>), grid, dim3(256), 0, stream, P);
+            if (P.scale_is_mul) hipLaunchKernelGGL((build_split_kernel<true>), grid, dim3(256), 0, stream, P);
+            else hipLaunchKernelGGL((build_split_kernel<false>), grid, dim3(256), 0, stream, P);
         }
     } else {
         // D = 256 with 4-aligned rows and 31-bit operand offsets: the 256 x 128 fp32 kernel

@@ -20,13 +20,11 @@ collective lands in a persistent receive buffer [world][chunk], and one HIP kern
 collective is RCCL over xGMI with the "nccl" backend (all_gather_into_tensor); any other backend
 (the CPU tests use gloo) gets all_gather into views of the same receive buffer.
 """
-import os
-
 import torch
 import torch.distributed as dist
 
 from . import _lib
-from .corr import _no_grad_inputs, _require_device_f32
+from ._lib import _no_grad_inputs, _require_device_f32
 from .layout import formats, untile
 
 
@@ -246,51 +244,17 @@ class RowShardedCorrBlock:
         """F.relu(conv1x1(self(coords), weight, bias)) for the full map on every rank: this rank's
         rows through the lookup + convc1 + ReLU (CorrBlock.lookup_conv1x1_relu, same `mode`), then
         the O-channel all-gather (exchange 2, fused form)."""
-        mode = mode or os.environ.get("ECORR_CONVC1", "split")
-        if mode not in ("split", "fused"):
-            raise ValueError(f"mode {mode!r}: expected 'split' or 'fused'")
+        mode = _lib.convc1_mode(mode, presplit=False)
         B, _, H, W = self._shape
         coords_rows = self._full_coords_rows(coords)
-        _require_device_f32("weight", weight)
-        _no_grad_inputs(weight, *(() if bias is None else (bias,)))
-        if weight.device != self._device or (bias is not None and bias.device != self._device):
-            raise RuntimeError("weight / bias are on a different device than the pyramid")
-        K = 2 * self.radius + 1
-        C = self.num_levels * K * K
-        O = weight.shape[0]
-        if weight.numel() != O * C:
-            raise RuntimeError(f"weight {tuple(weight.shape)} does not map {C} correlation channels")
-        if bias is not None:
-            _require_device_f32("bias", bias)
-            if bias.numel() != O:
-                raise RuntimeError(f"bias has {bias.numel()} elements, expected {O}")
-            bias = bias.contiguous()
-        if mode == "fused" and (O <= 0 or O % 64 != 0):
-            raise RuntimeError(f"{O} output channels: the fused kernel needs a positive multiple of 64")
-        if self.world == 1:
-            out = torch.empty((B, O, H, W), dtype=torch.float32, device=self._device)
-        else:
-            out = self._ex.send_slab(B, O, W, device=self._device)
-        with _lib.on_device(self._device):
-            if mode == "split":
-                wt = _lib.packed_conv1x1_weight(weight, O, C, "split", _lib.stream_of(out), self._wcache)
-                G = 3 * self.num_levels
-                corr = torch.empty((B, C, self.q_count), dtype=torch.float32, device=self._device)
-                qmax = torch.empty((B, G, self.q_count), dtype=torch.float32, device=self._device)
-                _lib.check(_lib.lib().ecorr_lookup_qmax(
-                    self._pyramid.data_ptr(), coords_rows.data_ptr(), B, H, W, self.q_count, self.num_levels,
-                    self.radius, corr.data_ptr(), qmax.data_ptr(), _lib.stream_of(out)),
-                    "RowShardedCorrBlock lookup (split convc1)")
-                _lib.check(_lib.lib().ecorr_conv1x1_relu_split(
-                    corr.data_ptr(), B, C, self.q_count, qmax.data_ptr(), G, wt.data_ptr(),
-                    None if bias is None else bias.data_ptr(), O, out.data_ptr(), _lib.stream_of(out)),
-                    "RowShardedCorrBlock lookup+conv1x1+relu (split)")
-                return out if self.world == 1 else self._ex.gather(B, O, W, self._device)
-            wt = _lib.packed_conv1x1_weight(weight, O, C, "fused", _lib.stream_of(out), self._wcache)
-            _lib.check(_lib.lib().ecorr_lookup_conv1x1_relu_packed(
-                self._pyramid.data_ptr(), coords_rows.data_ptr(), B, H, W, self.q_count, self.num_levels,
-                self.radius, wt.data_ptr(), None if bias is None else bias.data_ptr(), O, out.data_ptr(),
-                _lib.stream_of(out)), "RowShardedCorrBlock lookup+conv1x1+relu")
+
+        def alloc(O):   # this rank's rows: the whole map, or the persistent send slab
+            if self.world == 1:
+                return torch.empty((B, O, H, W), dtype=torch.float32, device=self._device)
+            return self._ex.send_slab(B, O, W, device=self._device)
+
+        out = _lib.lookup_conv1x1_relu(self._pyramid, coords_rows, (B, H, W), self.q_count, self.num_levels,
+                                       self.radius, weight, bias, mode, alloc, self._wcache, "RowShardedCorrBlock")
         if self.world == 1:
             return out
-        return self._ex.gather(B, O, W, self._device)                        # exchange 2 (fused)
+        return self._ex.gather(B, out.shape[1], W, self._device)             # exchange 2 (fused form)

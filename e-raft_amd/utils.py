@@ -6,7 +6,7 @@ coords_grid(batch, ht, wd, device=None)                      utils.py:24-27
 import torch
 
 from . import _lib
-from .corr import _no_grad_inputs, _require_device_f32
+from ._lib import _no_grad_inputs, _require_device_f32
 
 
 def bilinear_sampler(img, coords, mode="bilinear", mask=False):

@@ -29,7 +29,16 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "e-raft_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
-SOURCES = ["abi", "build", "conv", "lookup", "motion", "rows", "splat", "upsample", "voxel"]
+
+
+def _makefile_sources():
+    """Every source of libecorr.so: the Makefile's SRCS, without the .hip suffix."""
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        m = re.search(r"^SRCS\s*:=\s*(.*)$", f.read(), re.M)
+    return [s[:-len(".hip")] for s in m.group(1).split() if s.endswith(".hip")] if m else []
+
+
+SOURCES = _makefile_sources()
 WIDE = re.compile(r"buffer_store_(?:dwordx3|dwordx4|b96|b128)\s+v\[(\d+):(\d+)\],\s*\S+,\s*s\[\d+:\d+\],\s*(\S+)")
 VDST = re.compile(r"v_\S+\s+v(?:\[(\d+):(\d+)\]|(\d+))\b")
 
@@ -87,6 +96,7 @@ def compiled():
 
 
 def test_no_wide_store_with_sgpr_soffset(compiled):
+    assert "build" in SOURCES and "grad" in SOURCES, f"SRCS of the Makefile not read: {SOURCES}"   # build: _asm's flag
     for n in SOURCES:
         sgpr, hazards = scan(compiled[n])
         assert not sgpr, f"{n}.hip: wide buffer stores with an SGPR soffset: {sgpr[:3]}"

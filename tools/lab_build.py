@@ -220,9 +220,9 @@ PATCHES["l01oob"] = [("build.hip", "ok ? base + (int)(s * lsz * 4) : SOOB, 0, ST
 PATCHES["dmaoob"] = [("build.hip", "in ? kc * PANEL + c * 1024 + lane * 16 : SOOB, 0, 0, 0);", "in ? SOOB : SOOB, 0, 0, 0);")]
 PATCHES["qoob"] = [("build.hip", "rq, in ? qgo + kc * PANEL + i * 2048 : SOOB, 0, 0));", "rq, in ? SOOB : SOOB, 0, 0));"),
                    ("build.hip", "rq, in ? qgo + kc * PANEL + i * 2048 + 1024 : SOOB, 0, 0));", "rq, in ? SOOB : SOOB, 0, 0));")]
-# split-loop prefetch depth of the target panel (tree: 4 chunks / buffers)
+# LDS buffers of the split loop's target-panel ring (tree: 4)
 for _dt in (3, 5, 6):
-    PATCHES[f"dt{_dt}"] = [("build.hip", "constexpr int SDT = 4; ", f"constexpr int SDT = {_dt}; ")]
+    PATCHES[f"dt{_dt}"] = [("build.hip", "constexpr int SNBUF = 4; ", f"constexpr int SNBUF = {_dt}; ")]
 # timing only: every block reads the same query / target panels (all L2 hits, same traffic to the CUs)
 PATCHES["sameq"] = [("build.hip", "P.pk1 + ((int64_t)b * P.n_mt + qp) * pstride", "P.pk1")]
 PATCHES["samet"] = [("build.hip", "P.pk2 + ((int64_t)b * P.n_nt + nt) * pstride", "P.pk2")]
