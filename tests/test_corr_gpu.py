@@ -197,8 +197,9 @@ def test_errors_match_reference(ea):
 
 # Tile-geometry sweep: H % 8 = 0..7 (regular 8 x 16 tiles, 4 x 32 band tiles for remainders 1-4,
 # padded tile rows for 5-7), widths that are / are not multiples of 4, 16 and 32 (vector and
-# scalar loaders, partial band tiles), 1..5 levels (levels >= 4 pooled by pool2_kernel), tiled
-# and compact level formats.
+# scalar loaders, partial band tiles), 1..5 levels (levels >= 4 pooled by pool2_kernel).  Level 0 is
+# tiled and levels 1-3 interleaved in every case; the one level 4 here (2 x 3, of 36 x 52) is compact.
+# Tiled levels >= 4 and a level 5: test_slab_levels_ge4 below.
 GEOMETRY = [(1, 32, 60, 80, 4), (1, 16, 17, 20, 4), (2, 16, 19, 24, 3), (1, 8, 20, 36, 4),
             (1, 8, 21, 40, 2), (1, 16, 22, 18, 4), (1, 8, 23, 16, 1), (1, 16, 24, 44, 4),
             (1, 8, 25, 33, 4), (2, 16, 36, 52, 5), (1, 8, 12, 100, 4), (1, 16, 92, 160, 4)]
@@ -224,6 +225,74 @@ def test_geometry_vs_oracle(ea, geom):
     for i in range(1, L):
         assert oracle.same_bits(levels[i], ref_levels[i]), f"level {i}"
     assert oracle.same_bits(out, oracle.lookup(levels, coords, 4))
+
+
+# Levels >= 4 in the tiled format (level 4 = 4 x 7 with one tile per tile row, 4 x 17 with three) and a
+# compact level 5 made from a tiled level 4, at slab cost (C ABI, q_count query rows: item 1 of the
+# first case starts at row 120, inside an interleave group): both builds, then the lookup.
+# (B, H, W, L, q_begin, q_count, {level: ntx})
+SLAB_LEVELS = [(2, 64, 120, 6, 32 * 120, 120, {4: 1, 5: 0}), (1, 64, 272, 5, 30 * 272 + 50, 100, {4: 3})]
+
+
+@pytest.mark.parametrize("cfg", SLAB_LEVELS, ids=lambda c: "b%d_%dx%d_l%d_q%d" % (c[0], c[1], c[2], c[3], c[5]))
+def test_slab_levels_ge4(ea, cfg):
+    import ctypes
+    from eraft_amd import _lib
+    from eraft_amd.layout import formats, levels_of
+    B, H, W, L, q_begin, q, want = cfg
+    D, r = 32, 4
+    ntx = formats(H, W, L)
+    for lv, n in want.items():   # if the format rule changes, say so instead of silently covering less
+        assert ntx[lv] == n, f"level {lv} has format {ntx[lv]}, this test was written for {n}"
+    f1, f2 = prng.normal(61, (B, D, H, W)), prng.normal(62, (B, D, H, W))
+    slab = lambda a: np.ascontiguousarray(a.reshape(B, a.shape[1], H * W)[:, :, q_begin:q_begin + q])  # noqa: E731
+    d1, d2 = torch.from_numpy(slab(f1)).to(DEV), torch.from_numpy(f2).to(DEV)
+    _, _, off = _lib.layout(B * q, H, W, L)
+    lib, st = _lib.lib(), _lib.stream_of(d1)
+
+    def build(split):
+        pyr = torch.full((off[-1],), float("nan"), dtype=torch.float32, device=DEV)
+        if split:
+            n = ctypes.c_int64()
+            _lib.check(lib.ecorr_build_split_workspace_size(B, D, H, W, q, ctypes.byref(n)), "workspace size")
+            ws = torch.empty(n.value, dtype=torch.uint8, device=DEV)
+            _lib.check(lib.ecorr_build_split(d1.data_ptr(), d2.data_ptr(), B, D, H, W, q, L, pyr.data_ptr(),
+                                             ws.data_ptr(), st), "build split")
+        else:
+            _lib.check(lib.ecorr_build(d1.data_ptr(), d2.data_ptr(), B, D, H, W, q, L, pyr.data_ptr(), st), "build")
+        torch.cuda.synchronize()
+        return pyr
+
+    sets = {"s2p5": prng.coords_with_flow(63, B, H, W, 2.5)}
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.float32), np.arange(W, dtype=np.float32), indexing="ij")
+    edge = np.broadcast_to(np.stack([xs, ys])[None], (B, 2, H, W)).astype(np.float32).copy()
+    edge[:, 0, :, :4] = np.float32(-4.5) - edge[:, 0, :, :4]
+    edge[:, 0, :, -4:] += np.float32(3.7)
+    edge[:, 1, :2] = np.float32(-0.999)
+    edge[:, 1, -2:] = np.float32(H - 1) + np.float32(2.25)
+    sets["edge_left_right"] = edge                       # the slab's rows: windows over the left and right edges
+    sets["edge_top"] = np.roll(edge, H // 2, axis=2)     # rows 0 .. (above the image) rolled into the slab
+    sets["edge_bottom"] = np.roll(edge, -(H // 2 - 2), axis=2)
+    odd = prng.coords_with_flow(64, B, H, W, 6.0).astype(np.float32)
+    odd.reshape(B, 2, H * W)[0, :, q_begin:q_begin + 6] = np.array([[np.nan, np.inf, -np.inf, 1e9, -7.0e5, 3.0e7]] * 2,
+                                                                   dtype=np.float32)
+    sets["odd"] = odd
+    for split in (True, False):
+        pyr = build(split)
+        levels = [lv[:, 0].cpu().numpy() for lv in levels_of(pyr, B * q, H, W, L)]
+        what = "split" if split else "fp32"
+        assert oracle.normwise_err(levels[0], oracle.corr_level0(f1, f2, q_begin, q)) <= GEMM_TOL, what
+        ref_levels = oracle.pyramid_from_level0(levels[0], L)
+        for i in range(1, L):
+            assert oracle.same_bits(levels[i], ref_levels[i]), f"{what}: level {i}"
+        for name, c in sets.items():
+            cs = slab(c).reshape(B, 2, 1, q)
+            out = torch.empty((B, L * 81, q), dtype=torch.float32, device=DEV)
+            ct = torch.from_numpy(cs).to(DEV)
+            _lib.check(lib.ecorr_lookup(pyr.data_ptr(), ct.data_ptr(), B, H, W, q, L, r, out.data_ptr(), st), "lookup")
+            torch.cuda.synchronize()
+            assert oracle.same_bits(out.cpu().numpy().reshape(B, L * 81, 1, q), oracle.lookup(levels, cs, r)), \
+                f"{what}: {name}"
 
 
 # Column-pair window staging (every level width even, lookup_stage.h) vs single columns (some level
