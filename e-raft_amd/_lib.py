@@ -177,6 +177,15 @@ def stream_of(t: torch.Tensor):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def tensor_version(t: torch.Tensor) -> int:
+    """t's version counter, -1 for an inference tensor: it has none (in-place updates, legal under
+    inference_mode, are then not seen)."""
+    try:
+        return t._version
+    except RuntimeError:
+        return -1
+
+
 _same_device = contextlib.nullcontext()
 
 
@@ -260,10 +269,7 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
 # of ONE block is not seen -- weights are fixed during a forward.  The pack runs on the consumer's
 # stream `st`, so the lookups that read it are ordered after it.
 def packed_conv1x1_weight(weight, O, C, kind, st, cache):
-    try:
-        version = weight._version
-    except RuntimeError:   # inference tensor: no version counter
-        version = -1
+    version = tensor_version(weight)
     key = (kind, O, C)
     ent = cache.get(key)
     if ent is not None and ent[0] is weight and ent[1] == (weight.data_ptr(), version):
@@ -288,6 +294,17 @@ def packed_conv1x1_weight(weight, O, C, kind, st, cache):
         check(lib().ecorr_conv1x1_pack(wt.data_ptr(), O, C, packed.data_ptr(), st), "convc1 weight pack")
     cache[key] = (weight, (weight.data_ptr(), version), packed)
     return packed
+
+
+def lookup(pyramid, coords, shape, q_count, levels, radius, out, what):
+    """The ecorr_lookup launch of every block: the q_count queries of contiguous coords
+    [B][2][q_count] into out ([B][C][q_count] fp32, returned), on the current stream of the pyramid's
+    device.  shape = (B, H, W) of the build; what: the class name for error texts."""
+    B, H, W = shape
+    with on_device(pyramid.device):
+        check(lib().ecorr_lookup(pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius,
+                                 out.data_ptr(), stream_of(out)), f"{what} lookup")
+    return out
 
 
 def convc1_mode(mode, presplit):

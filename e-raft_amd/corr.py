@@ -48,14 +48,7 @@ import torch
 
 from . import _lib
 from ._lib import _no_grad_inputs, _require_device_f32
-from .layout import formats, untile
-
-
-def _version(t):
-    try:
-        return t._version
-    except RuntimeError:   # inference tensor: no version counter (and no in-place updates)
-        return -1
+from .layout import levels_of
 
 
 class _GradState:
@@ -111,13 +104,9 @@ class _LookupFn(torch.autograd.Function):
         ctx.save_for_backward(coords)   # versioned: an in-place change before backward raises
         B, _, H, W = state.shape
         K = 2 * state.radius + 1
-        cc = coords.contiguous()
-        with _lib.on_device(state.device):
-            out = torch.empty((B, state.levels * K * K, H, W), dtype=torch.float32, device=state.device)
-            _lib.check(_lib.lib().ecorr_lookup(
-                pyramid.data_ptr(), cc.data_ptr(), B, H, W, H * W, state.levels, state.radius,
-                out.data_ptr(), _lib.stream_of(cc)), "CorrBlock lookup")
-        return out
+        out = torch.empty((B, state.levels * K * K, H, W), dtype=torch.float32, device=state.device)
+        return _lib.lookup(pyramid, coords.contiguous(), (B, H, W), H * W, state.levels, state.radius, out,
+                           "CorrBlock")
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -194,7 +183,8 @@ class CorrBlock:
         # presplit convc1: the column scales come from the fmaps (ecorr_split_column_scale), computed
         # on the first presplit call; weak references and version counters, so the block neither
         # keeps the fmaps alive nor trusts them after an in-place change (then: the split mode)
-        self._fmap_refs = (weakref.ref(fmap1), weakref.ref(fmap2), _version(fmap1), _version(fmap2))
+        self._fmap_refs = (weakref.ref(fmap1), weakref.ref(fmap2),
+                           _lib.tensor_version(fmap1), _lib.tensor_version(fmap2))
         self._colscale = None
         self._grad = self._handle = None
         if live:
@@ -205,11 +195,7 @@ class CorrBlock:
     def corr_pyramid(self):
         """Reference-layout levels [B*H*W, 1, h_i, w_i] (corr.py:16-27), materialized on demand."""
         if self._levels_cache is None:
-            ntx = formats(self._shape[2], self._shape[3], self.num_levels)
-            self._levels_cache = [
-                untile(self._pyramid[self._off[i]:self._off[i + 1]], self._rows, self._h[i], self._w[i],
-                       ntx[i], i)
-                for i in range(self.num_levels)]
+            self._levels_cache = levels_of(self._pyramid, self._rows, self._shape[2], self._shape[3], self.num_levels)
         return self._levels_cache
 
     def __call__(self, coords):
@@ -228,13 +214,8 @@ class CorrBlock:
             return _LookupFn.apply(self._handle, coords, self._grad, self._pyramid)
         coords = coords.contiguous()   # the reference accepts any strides (permute + reshape)
         K = 2 * self.radius + 1
-        C = self.num_levels * K * K
-        with _lib.on_device(self._device):
-            out = torch.empty((B, C, H, W), dtype=torch.float32, device=self._device)
-            _lib.check(_lib.lib().ecorr_lookup(
-                self._pyramid.data_ptr(), coords.data_ptr(), B, H, W, H * W, self.num_levels,
-                self.radius, out.data_ptr(), _lib.stream_of(coords)), "CorrBlock lookup")
-        return out
+        out = torch.empty((B, self.num_levels * K * K, H, W), dtype=torch.float32, device=self._device)
+        return _lib.lookup(self._pyramid, coords, (B, H, W), H * W, self.num_levels, self.radius, out, "CorrBlock")
 
     def lookup_conv1x1_relu(self, coords, weight, bias=None, mode=None):
         """F.relu(conv1x1(self(coords), weight, bias)): the lookup followed by
@@ -273,7 +254,7 @@ class CorrBlock:
         if self._colscale is None:
             r1, r2, v1, v2 = self._fmap_refs
             f1, f2 = r1(), r2()
-            if f1 is None or f2 is None or _version(f1) != v1 or _version(f2) != v2:
+            if f1 is None or f2 is None or _lib.tensor_version(f1) != v1 or _lib.tensor_version(f2) != v2:
                 return None
             B, D, H, W = self._shape
             sc = torch.empty(B * H * W + B, dtype=torch.int32, device=self._device)

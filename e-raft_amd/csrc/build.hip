@@ -25,19 +25,13 @@
 // §3.1 keeps the record); lab builds for new A/Bs are separate .so files (tools/).
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "split_f16.h"
 
 #include <type_traits>
 
 namespace ecorr {
 
 namespace {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-typedef unsigned uint2v __attribute__((ext_vector_type(2)));
 
 constexpr int TBH = 8, TBW = 16;  // regular target block (rows x cols) of one n-tile
 constexpr int PANEL = 8192;       // bytes of one (128-pixel tile, 16-deep K chunk) operand panel
@@ -55,17 +49,6 @@ __device__ __forceinline__ float pool4_v(float a, float b, float c, float d) {
     asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(s), "v"(d));
     asm("v_mul_f32 %0, 0.25, %1" : "=v"(s) : "v"(s));
     return s;
-}
-
-// 2^e as a float, e in [-126, 127]
-__device__ __forceinline__ float exp2i(int e) { return __int_as_float((e + 127) << 23); }
-
-// s_waitcnt vmcnt(N) with lgkmcnt(0) (LGKM0) or left alone; expcnt never waited (gfx9 encoding:
-// vmcnt bits 3:0 and 15:14)
-template <int N, bool LGKM0>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt field");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (LGKM0 ? 0 : (15 << 8)));
 }
 
 // Bijective XCD-aware remap (cdna_hip_programming.md §5 T1): consecutive logical tiles land on
@@ -1263,16 +1246,8 @@ __global__ __launch_bounds__(256, 2) void build_f32_kernel(BuildParams P) {
 // edges) and k >= D are zeros.  ISB = 0: fmap1 slab, tile = 128 consecutive queries; ISB = 1:
 // fmap2, tile = the n-tile's targets in split_target order.  Block = 64 positions x 4 chunk
 // quarters; the D <= 256 values of a thread stay in registers between the max and the split.
-__device__ __forceinline__ void split_f16(const float (&v)[8], float s, halfx8& hi, halfx8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = v[j] * s;
-        const _Float16 h = (_Float16)x;
-        hi[j] = h;
-        lo[j] = (_Float16)(x - (float)h);
-    }
-}
-
+// (split_exponent and split_f16: split_f16.h.)
+//
 // L16: the panel layout of build_split16_kernel (16 KB per 128-pixel tile and 32-deep chunk pair:
 // [16-pixel group g][hi | lo][k block kb][pixel r][8 halves], k = 8 kb + j within the pair; fmap2
 // positions in split16_target order) instead of build_split_kernel's 8-KB chunk panels.
@@ -1344,10 +1319,7 @@ __device__ __forceinline__ void pack_body(const float* __restrict__ x, const Bui
     __syncthreads();
     const int l = threadIdx.x & 63;
     m = fmaxf(fmaxf(red[0][l], red[1][l]), fmaxf(red[2][l], red[3][l]));
-    int E = 0;
-    frexpf(m, &E);
-    int e = (m > 0.f && m <= 3.4028235e38f) ? 15 - E : 0;
-    e = e < -126 ? -126 : (e > 126 ? 126 : e);
+    const int e = split_exponent(m);
     if (qtr == 0 && pix >= 0) ex[(int64_t)b * N + pix] = e;
     const float s = exp2i(e);
     const int ntiles = ISB ? P.n_nt : P.n_mt;
@@ -1874,10 +1846,7 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
             if (s16) hipLaunchKernelGGL((pack_both_kernel<true>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
             else hipLaunchKernelGGL((pack_both_kernel<false>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
         }
-        if (!(stages & 2)) {
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
-        }
+        if (!(stages & 2)) return hip_status();
         const dim3 grid((unsigned)ntiles);
         if (s16) {
             if (P.scale_is_mul) hipLaunchKernelGGL((build_split16_kernel<true>), grid, dim3(256), 0, stream, P);
@@ -1908,18 +1877,16 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
             else hipLaunchKernelGGL((build_kernel<false, false>), grid, block, 0, stream, P);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ECORR_EHIP - (int)e;
+    int st = hip_status();
     const int64_t rows = (int64_t)B * P.q_count;
-    for (int i = 4; i < levels; ++i) {
+    for (int i = 4; i < levels && st == ECORR_OK; ++i) {
         const int64_t n = rows * g.h[i] * g.w[i];
         const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
         hipLaunchKernelGGL(pool2_kernel, dim3(grid), dim3(256), 0, stream, pyramid + g.off[i - 1], pyramid + g.off[i],
                            rows, g.h[i - 1], g.w[i - 1], i - 1, g.ntx[i - 1], g.sz[i - 1], g.ntx[i], g.sz[i]);
-        e = hipGetLastError();
-        if (e != hipSuccess) return ECORR_EHIP - (int)e;
+        st = hip_status();
     }
-    return ECORR_OK;
+    return st;
 }
 
 }  // namespace ecorr

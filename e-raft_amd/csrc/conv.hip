@@ -32,16 +32,13 @@
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "split_f16.h"
 
 #include <algorithm>
 
 namespace ecorr {
 
 namespace {
-
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
 
 constexpr int SQ = 64;                 // queries per workgroup
 constexpr int SO = 256;                // output channels per workgroup (8 row blocks of 32)
@@ -51,26 +48,6 @@ constexpr int SCHUNK = 8 * 2 * 64 * 16;   // bytes per packed weight chunk: [row
 
 __host__ __device__ constexpr int split_chunks(int C) { return (C + SKC - 1) / SKC; }
 __host__ __device__ constexpr int split_oblocks(int O) { return (O + SO - 1) / SO; }
-
-__device__ __forceinline__ float pow2(int e) { return __int_as_float((e + 127) << 23); }
-
-// e such that m 2^e lies in [2^14, 2^15); 0 for a zero or non-finite maximum (build.hip pack_body)
-__device__ __forceinline__ int split_exponent(float m) {
-    int E = 0;
-    frexpf(m, &E);
-    const int e = (m > 0.f && m <= 3.4028235e38f) ? 15 - E : 0;
-    return e < -126 ? -126 : (e > 126 ? 126 : e);
-}
-
-__device__ __forceinline__ void split8(const float (&v)[8], float s, halfx8& hi, halfx8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = v[j] * s;
-        const _Float16 h = (_Float16)x;
-        hi[j] = h;
-        lo[j] = (_Float16)(x - (float)h);
-    }
-}
 
 // Packed weight: for output block ob (256 channels) and chunk c, 16 KB at (ob nkc + c) SCHUNK:
 // [row block rb][hi | lo][lane l][8 halves] = W[256 ob + 32 rb + (l & 31)][16 c + 8 (l >> 5) + j]
@@ -88,7 +65,7 @@ __global__ __launch_bounds__(SNT) void split_pack_kernel(const float* __restrict
     if (o < O)
         for (int k = 0; k < C; ++k) m = fmaxf(m, fabsf(wt[(int64_t)o * C + k]));
     const int e = split_exponent(m);
-    sc[t] = pow2(e);
+    sc[t] = exp2i(e);
     reinterpret_cast<int*>(packed + (int64_t)nob * nkc * SCHUNK)[o] = e;
     __syncthreads();
     char* base = packed + (int64_t)ob * nkc * SCHUNK;
@@ -102,16 +79,9 @@ __global__ __launch_bounds__(SNT) void split_pack_kernel(const float* __restrict
             v[j] = (oo < O && ch >= 0) ? wt[(int64_t)oo * C + ch] : 0.f;
         }
         halfx8 hi, lo;
-        split8(v, sc[r], hi, lo);
+        split_f16(v, sc[r], hi, lo);
         *reinterpret_cast<halfx8*>(base + (int64_t)i * 16) = part ? lo : hi;
     }
-}
-
-// s_waitcnt vmcnt(N) only (gfx9 encoding: vmcnt bits 3:0 and 15:14; expcnt, lgkmcnt not waited)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt field");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 
 // The weight chunks go global -> LDS by LDS-DMA (no staging registers; through registers it was
@@ -164,9 +134,8 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
     // v[0..3] = the hi halves, v[4..7] = the lo halves of group 2 c + kh (chunk offset in soffset)
     auto load_b = [&](int c, float (&v)[8]) __attribute__((always_inline)) {
         if constexpr (PRE) {
-            typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-            const u4 h = __builtin_amdgcn_raw_buffer_load_b128(csrc, cbase, c * 4 * Q * 16, 0);
-            const u4 l = __builtin_amdgcn_raw_buffer_load_b128(csrc, cbase + Q * 16, c * 4 * Q * 16, 0);
+            const uint4v h = __builtin_amdgcn_raw_buffer_load_b128(csrc, cbase, c * 4 * Q * 16, 0);
+            const uint4v l = __builtin_amdgcn_raw_buffer_load_b128(csrc, cbase + Q * 16, c * 4 * Q * 16, 0);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 v[j] = __uint_as_float(h[j]);
@@ -257,7 +226,7 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (!PRE) eq = split_exponent(fmaxf(red[0][qi], red[1][qi]));
-    const float sq = pow2(eq);
+    const float sq = exp2i(eq);
 
     floatx16 acc[4];
 #pragma unroll
@@ -276,13 +245,12 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
         __builtin_amdgcn_sched_barrier(0);   // issued here, ahead of this chunk's work
         halfx8 bh, bl;
         if constexpr (PRE) {
-            typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-            bh = __builtin_bit_cast(halfx8, u4{__float_as_uint(cur[0]), __float_as_uint(cur[1]), __float_as_uint(cur[2]),
+            bh = __builtin_bit_cast(halfx8, uint4v{__float_as_uint(cur[0]), __float_as_uint(cur[1]), __float_as_uint(cur[2]),
                                                __float_as_uint(cur[3])});
-            bl = __builtin_bit_cast(halfx8, u4{__float_as_uint(cur[4]), __float_as_uint(cur[5]), __float_as_uint(cur[6]),
+            bl = __builtin_bit_cast(halfx8, uint4v{__float_as_uint(cur[4]), __float_as_uint(cur[5]), __float_as_uint(cur[6]),
                                                __float_as_uint(cur[7])});
         } else {
-            split8(cur, sq, bh, bl);
+            split_f16(cur, sq, bh, bl);
         }
         const char* wb = wbuf[c % NB] + lane * 16;
         // A fragments double-buffered: tile i + 2's pair is read right after tile i's MFMAs issue, so
@@ -368,8 +336,7 @@ int launch_conv1x1_split_pack(const float* wt, int O, int C, void* packed, hipSt
     if (perm_levels && (perm_levels < 1 || perm_levels > 4 || C != 81 * perm_levels)) return ECORR_EINVAL;
     hipLaunchKernelGGL(split_pack_kernel, dim3(split_oblocks(O)), dim3(SNT), 0, stream, wt, O, C, (char*)packed,
                        perm_levels);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
+    return hip_status();
 }
 
 int launch_conv1x1_relu_split(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
@@ -385,8 +352,7 @@ int launch_conv1x1_relu_split(const float* in, int B, int C, int Q, const float*
     const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
     hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax, G,
                        (const char*)packed, bias, O, out, nullptr);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
+    return hip_status();
 }
 
 int launch_conv1x1_relu_presplit(const void* in, int B, int levels, int Q, const int* scale, const void* packed,
@@ -401,8 +367,7 @@ int launch_conv1x1_relu_presplit(const void* in, int B, int levels, int Q, const
     const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
     hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, true>), grid, dim3(SNT), 0, stream, (const float*)in, C, Q,
                        nullptr, 0, (const char*)packed, bias, O, out, scale);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
+    return hip_status();
 }
 
 }  // namespace ecorr

@@ -20,6 +20,12 @@ constexpr int kTileH = 4, kTileW = 8, kTile = kTileH * kTileW;
 __host__ __device__ __forceinline__ int tiled_off(int y, int x, int ntx) {
     return (((y >> 2) * ntx + (x >> 3)) << 5) + ((y & 3) << 3) + (x & 7);
 }
+// its inverse: pixel (y, x) of stored cell c (a padding cell's pixel lies outside the image)
+__host__ __device__ __forceinline__ void tiled_cell_yx(int c, int ntx, int& y, int& x) {
+    const int tile = c >> 5;
+    y = (tile / ntx) * kTileH + ((c >> 3) & 3);
+    x = (tile % ntx) * kTileW + (c & 7);
+}
 __host__ __device__ __forceinline__ int pad_h(int h) { return (h + kTileH - 1) & ~(kTileH - 1); }
 __host__ __device__ __forceinline__ int pad_w(int w) { return (w + kTileW - 1) & ~(kTileW - 1); }
 
@@ -65,6 +71,47 @@ __device__ __forceinline__ float unnormalize(float x, float size_m1, float half_
     return __fmul_rn(__fadd_rn(g, 1.0f), half_size_m1);
 }
 
+// One coordinate chain of the lookup (corr.py:41-43, utils.py:11-12, grid_sampler unnormalize): the
+// tap at offset d = o - r (o = 0 .. 2r) of the axis whose scaled coordinate is cs = coords / 2^lv, on
+// a level side of m1 + 1 pixels -> floor and fraction.  The forward (lookup_stage.h coord_chain<R>)
+// and the backward (grad.hip) both call this, so their supports cannot differ.
+__device__ __forceinline__ void coord_chain(float cs, int d, float m1, float& f, float& wgt) {
+    const float c = __fadd_rn(cs, (float)d);
+    const float v = unnormalize(c, m1, m1 * 0.5f);
+    f = floorf(v);
+    wgt = __fsub_rn(v, f);
+}
+
+// Whether the floors of a query's first / last taps (x0, xl), (y0, yl) bound a window of at most
+// span + 1 floors per axis (md 0, else 1), and then its origin and the corner columns / rows it
+// spans, [x0, xl + 1]: nx, ny <= span + 2 (all zeros when it does not fit).  Every step of the chain
+// (exact-or-rounded add of the offset, the normalize / unnormalize roundings by positive factors,
+// floor) is monotone, so the floors are non-decreasing in the offset and the end taps bound the
+// whole window; NaN / inf / huge coordinates do not fit (the forward gathers them directly, the
+// backward walks them serially, and they fail every in-range test there).
+struct WindowFit { int md, x0, y0, nx, ny; };
+__device__ __forceinline__ WindowFit window_fit(float x0, float xl, float y0, float yl, int span) {
+    bool ok = fabsf(x0) < 1.0e7f && fabsf(y0) < 1.0e7f;  // false for NaN / inf / huge
+    const float dx = xl - x0, dy = yl - y0;   // exact: integers < 2^24
+    ok &= (dx >= 0.0f) & (dx <= (float)span) & (dy >= 0.0f) & (dy <= (float)span);
+    WindowFit f;
+    f.md = ok ? 0 : 1;
+    f.x0 = ok ? (int)x0 : 0;
+    f.y0 = ok ? (int)y0 : 0;
+    f.nx = ok ? (int)dx + 2 : 0;
+    f.ny = ok ? (int)dy + 2 : 0;
+    return f;
+}
+
+// grid_sample's zeros padding, tested in float: NaN, +-inf and huge floors are outside, exactly as
+// ATen's int32-converted masks have them.  axis_in: one axis alone (the backward's separable passes);
+// it is the two-axis test with a constant second axis, not the other way round, because the corner
+// fetches' instruction streams depend on the association of the four compares.
+__device__ __forceinline__ bool in_image(int h, int w, float fx, float fy) {
+    return (fx >= 0.0f) & (fx < (float)w) & (fy >= 0.0f) & (fy < (float)h);
+}
+__device__ __forceinline__ bool axis_in(float f, int n) { return in_image(1, n, f, 0.0f); }
+
 // Bilinear blend exactly as ATen's AVX512 grid_sampler (nw product, then FMA chain).
 // w = x-frac, n = y-frac; out-of-image corners must already be 0.
 __device__ __forceinline__ float blend(float vnw, float vne, float vsw, float vse, float w, float n) {
@@ -77,13 +124,11 @@ __device__ __forceinline__ float blend(float vnw, float vne, float vsw, float vs
     return acc;
 }
 
-// Zeros-padding corner fetch by float coordinates (float compare: NaN and +-huge read 0, exactly
-// as ATen's int32-converted masks do).  Used by the generic / fallback paths only.
+// Zeros-padding corner fetch by float coordinates (in_image).  Used by the generic / fallback paths only.
 // ntx <= 0: row-major image (bilinear_sampler, compact levels); otherwise a tiled pyramid level.
 __device__ __forceinline__ float corner(const float* __restrict__ img, int h, int w, float fx, float fy,
                                         int ntx = 0) {
-    const bool in = (fx >= 0.0f) & (fx < (float)w) & (fy >= 0.0f) & (fy < (float)h);
-    if (!in) return 0.0f;
+    if (!in_image(h, w, fx, fy)) return 0.0f;
     const int y = (int)fy, x = (int)fx;
     return img[ntx <= 0 ? (int64_t)y * w + x : (int64_t)tiled_off(y, x, ntx)];
 }
@@ -91,8 +136,7 @@ __device__ __forceinline__ float corner(const float* __restrict__ img, int h, in
 // The same corner fetch from pyramid level lv (base lvbase, any format) for query row R.
 __device__ __forceinline__ float level_corner(const float* __restrict__ lvbase, int64_t R, int lv, int ntx, int h,
                                               int w, int64_t sz, float fx, float fy) {
-    const bool in = (fx >= 0.0f) & (fx < (float)w) & (fy >= 0.0f) & (fy < (float)h);
-    if (!in) return 0.0f;
+    if (!in_image(h, w, fx, fy)) return 0.0f;
     return lvbase[pix_off(R, (int)fy, (int)fx, lv, ntx, w, sz)];
 }
 

@@ -7,6 +7,12 @@
 
 namespace ecorr {
 
+// The status every launch_* returns after its launches: the runtime's last error as an ECORR code.
+inline int hip_status() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
+}
+
 // Pyramid storage geometry (include/ecorr.h), computed once by pyramid_geometry() (abi.hip) and
 // shared by the build and the lookup.
 struct PyrGeom {

@@ -23,25 +23,12 @@ namespace {
 
 constexpr int NT = 256;
 
-inline int hip_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
-}
-
 // ---------------------------------------------------------------------------------------------
 // lookup backward
 // ---------------------------------------------------------------------------------------------
-// The forward's tap chain (lookup_stage.h coord_chain): floor and fraction of tap o of a coordinate.
-__device__ __forceinline__ void tap_chain(float cs, int o, int r, float m1, float& f, float& wgt) {
-    const float c = __fadd_rn(cs, (float)(o - r));
-    const float v = unnormalize(c, m1, m1 * 0.5f);
-    f = floorf(v);
-    wgt = __fsub_rn(v, f);
-}
-
-// level_corner's float in-range test on one axis (NaN, +-inf and huge floors fail it)
-__device__ __forceinline__ bool axis_in(float f, int n) { return (f >= 0.0f) & (f < (float)n); }
-
+// The tap chains, the window fit and the in-range test are the forward's own (ecorr_device.h
+// coord_chain, window_fit, axis_in): the backward's support is the forward's by construction.
+//
 // LDS (floats), g = query of the block innermost so that lanes = queries never share a bank:
 //   cf / cw [K][QB]      floor (as float) and fraction of the current axis' K taps
 //   org     [3][QB]      window origin x, y and mode (0 window, 1 serial, 2 no query) as ints
@@ -75,7 +62,7 @@ __global__ __launch_bounds__(NT) void lookup_backward_kernel(LookupGradParams P,
     for (int i = tid; i < K * QB; i += NT) {
         const int g = i % QB, o = i / QB;
         float f = 0.0f, wg = 0.0f;
-        if (q0 + g < P.q_count) tap_chain(__fmul_rn(cxp[q0 + g], inv), o, r, wm1, f, wg);
+        if (q0 + g < P.q_count) coord_chain(__fmul_rn(cxp[q0 + g], inv), o - r, wm1, f, wg);
         cf[o * QB + g] = f;
         cw[o * QB + g] = wg;
     }
@@ -84,19 +71,12 @@ __global__ __launch_bounds__(NT) void lookup_backward_kernel(LookupGradParams P,
         if (q0 + g < P.q_count) {
             const float cx = __fmul_rn(cxp[q0 + g], inv), cy = __fmul_rn(cyp[q0 + g], inv);
             float x0, xl, y0, yl, d;
-            tap_chain(cx, 0, r, wm1, x0, d);
-            tap_chain(cx, K - 1, r, wm1, xl, d);
-            tap_chain(cy, 0, r, hm1, y0, d);
-            tap_chain(cy, K - 1, r, hm1, yl, d);
-            // as the forward's window_origin: the floors are monotone in the tap, so the end taps
-            // bound the window; NaN / inf / huge coordinates take the serial path (and fail every
-            // in-range test there)
-            bool ok = fabsf(x0) < 1.0e7f && fabsf(y0) < 1.0e7f;
-            const float dx = xl - x0, dy = yl - y0;
-            ok &= (dx >= 0.0f) & (dx <= (float)(S - 2)) & (dy >= 0.0f) & (dy <= (float)(S - 2));
-            md = ok ? 0 : 1;
-            X0 = ok ? (int)x0 : 0;
-            Y0 = ok ? (int)y0 : 0;
+            coord_chain(cx, -r, wm1, x0, d);
+            coord_chain(cx, r, wm1, xl, d);
+            coord_chain(cy, -r, hm1, y0, d);
+            coord_chain(cy, r, hm1, yl, d);
+            const WindowFit f = window_fit(x0, xl, y0, yl, S - 2);
+            md = f.md, X0 = f.x0, Y0 = f.y0;   // md 1: the serial path
         }
         org[0 * QB + g] = X0;
         org[1 * QB + g] = Y0;
@@ -131,7 +111,7 @@ __global__ __launch_bounds__(NT) void lookup_backward_kernel(LookupGradParams P,
     for (int i = tid; i < K * QB; i += NT) {
         const int g = i % QB, o = i / QB;
         float f = 0.0f, wg = 0.0f;
-        if (q0 + g < P.q_count) tap_chain(__fmul_rn(cyp[q0 + g], inv), o, r, hm1, f, wg);
+        if (q0 + g < P.q_count) coord_chain(__fmul_rn(cyp[q0 + g], inv), o - r, hm1, f, wg);
         cf[o * QB + g] = f;
         cw[o * QB + g] = wg;
     }
@@ -191,10 +171,10 @@ __global__ __launch_bounds__(NT) void lookup_backward_kernel(LookupGradParams P,
         const float cx = __fmul_rn(cxp[q0 + g], inv), cy = __fmul_rn(cyp[q0 + g], inv);
         for (int a = 0; a < K; ++a) {
             float fx, wx;
-            tap_chain(cx, a, r, wm1, fx, wx);
+            coord_chain(cx, a - r, wm1, fx, wx);
             for (int bb = 0; bb < K; ++bb) {
                 float fy, wy;
-                tap_chain(cy, bb, r, hm1, fy, wy);
+                coord_chain(cy, bb - r, hm1, fy, wy);
                 const float go = gout[(int64_t)(a * K + bb) * Q + q0 + g];
                 const float ex = __fsub_rn(1.0f, wx), sy = __fsub_rn(1.0f, wy);
                 const float xs[2] = {fx, __fadd_rn(fx, 1.0f)}, ys[2] = {fy, __fadd_rn(fy, 1.0f)};
@@ -219,8 +199,8 @@ __global__ __launch_bounds__(NT) void fold_kernel(LookupGradParams P, int64_t ro
     const int64_t n = rows * sz;
     for (int64_t idx = blockIdx.x * (int64_t)NT + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * NT) {
         const int64_t R = idx / sz;
-        const int c = (int)(idx - R * sz);
-        const int tile = c >> 5, y = (tile / ntx) * kTileH + ((c >> 3) & 3), x = (tile % ntx) * kTileW + (c & 7);
+        int y, x;
+        tiled_cell_yx((int)(idx - R * sz), ntx, y, x);
         if (y >= H || x >= W) continue;
         // coarsest first; a pixel outside level l (floor pooling dropped it) is outside every coarser one
         float t = 0.0f;
@@ -245,6 +225,8 @@ __global__ __launch_bounds__(NT) void fold_kernel(LookupGradParams P, int64_t ro
 // of one row (one 4 x 8 tile).  Fragments as build_f32_kernel: A lane (m, kh) = op[m][2 s + kh],
 // B lane (n, kh) = T(n, 2 s + kh), C register r of lane (n, kh) = row (r & 3) + 8 (r >> 2) + 4 kh.
 // ---------------------------------------------------------------------------------------------
+// (a local typedef, not split_f16.h's: tools/grad_emul.py rewrites this line to compile the file on
+// the CPU, where the ext_vector_type MFMA accumulator has no equivalent)
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int GD = 256;   // d rows per pass
@@ -275,7 +257,8 @@ __global__ __launch_bounds__(NT) void build_backward_kernel(BuildGradParams P) {
     // pixel of a stored cell, or -1 for a padding cell
     auto cell_pixel = [&](int c) -> int {
         if (c >= sz) return -1;
-        const int tile = c >> 5, y = (tile / ntx) * kTileH + ((c >> 3) & 3), x = (tile % ntx) * kTileW + (c & 7);
+        int y, x;
+        tiled_cell_yx(c, ntx, y, x);
         return (y < H && x < W) ? y * W + x : -1;
     };
 

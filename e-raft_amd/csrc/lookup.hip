@@ -13,6 +13,7 @@
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
 #include "lookup_stage.h"
+#include "split_f16.h"
 
 namespace ecorr {
 
@@ -124,19 +125,17 @@ __global__ __launch_bounds__(3 * QB) void lookup_cols_reg(LookupParams P) {
     // halves k = 24 .. 26 go through LDS to the level's two leftover groups 9 L + 2 lv (+ 1), written
     // whole by waves 0 and 1 after the exchange; default store policy (the conv reads them right
     // back).  Wide stores keep soffset = 0 (tests/test_isa_store_hazard.py).
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     const int64_t pbytes = PRESPLIT ? presplit_bytes_per_item(presplit_positions(P.levels), P.q_count) : 0;
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<char*>(P.out) + (int64_t)b * pbytes, 0, (int)pbytes, 0x00020000);
-    const float psc = PRESPLIT && valid ? __int_as_float((P.scale[(int64_t)b * P.q_count + p] + 127) << 23) : 0.0f;
+    const float psc = PRESPLIT && valid ? exp2i(P.scale[(int64_t)b * P.q_count + p]) : 0.0f;
     uint32_t left[3] = {0, 0, 0};   // presplit: the leftover halves, hi | lo << 16
     auto put = [&](int k, float v) __attribute__((always_inline)) {
         vv[k] = v;
         const int Q = P.q_count;
         if (k % 8 == 7 && k < 24) {
             const int j = k / 8;
-            h8 hi, lo;
+            halfx8 hi, lo;
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const float x = __fmul_rn(vv[8 * j + t], psc);
@@ -145,8 +144,8 @@ __global__ __launch_bounds__(3 * QB) void lookup_cols_reg(LookupParams P) {
                 lo[t] = (_Float16)__fsub_rn(x, (float)h);
             }
             const int off = ((9 * lv + 3 * part + j) * 2 * Q + p) * 16;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, hi), prs, off, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, lo), prs, off + Q * 16, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, hi), prs, off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, lo), prs, off + Q * 16, 0, 0);
         }
         if (k >= 24) {
             const float x = __fmul_rn(v, psc);
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(3 * QB) void lookup_cols_reg(LookupParams P) {
         for (int i = 0; i < 3; ++i) xch[(3 * part + i) * QB + g] = left[i];
         __syncthreads();
         if (part < 2 && md != 2) {   // wave 0: leftovers 0-7, wave 1: leftover 8 + 7 zero halves
-            h8 hi, lo;
+            halfx8 hi, lo;
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const uint32_t u = (part == 0 || t == 0) ? xch[(8 * part + t) * QB + g] : 0u;
@@ -217,8 +216,8 @@ __global__ __launch_bounds__(3 * QB) void lookup_cols_reg(LookupParams P) {
             }
             const int Q = P.q_count;
             const int off = ((9 * P.levels + 2 * lv + part) * 2 * Q + p) * 16;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, hi), prs, off, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, lo), prs, off + Q * 16, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, hi), prs, off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, lo), prs, off + Q * 16, 0, 0);
         }
     }
 }
@@ -292,12 +291,6 @@ __global__ __launch_bounds__(NT) void coords_grid_kernel(int B, int H, int W, fl
 // falls under f16's normal range (scaled |x| < 2^-3).  The maxima are over finite values: a sample
 // touching a non-finite fmap value is non-finite itself (and NaNs its query in the conv, the split
 // contract), every other sample is bounded by the finite values it was made of.
-__device__ __forceinline__ int colscale_exponent(float m) {   // conv.hip split_exponent
-    int E = 0;
-    frexpf(m, &E);
-    const int e = (m > 0.f && m <= 3.4028235e38f) ? 15 - E : 0;
-    return e < -126 ? -126 : (e > 126 ? 126 : e);
-}
 
 // max |f2| (finite) per batch item as float bits (non-negative floats order as unsigned ints)
 __global__ __launch_bounds__(NT) void colscale_m2_kernel(const float* __restrict__ f2, int64_t n,
@@ -342,18 +335,13 @@ __global__ __launch_bounds__(NT) void colscale_kernel(const float* __restrict__ 
         const unsigned u = __float_as_uint(x[(int64_t)d * Q]) & 0x7fffffffu;
         m = u < 0x7f800000u ? max(m, u) : m;
     }
-    const int s = colscale_exponent(__uint_as_float(m)) + colscale_exponent(__uint_as_float(m2[b])) - 15 - hd;
+    const int s = split_exponent(__uint_as_float(m)) + split_exponent(__uint_as_float(m2[b])) - 15 - hd;
     scale[i] = s < -126 ? -126 : (s > 126 ? 126 : s);
 }
 
 inline unsigned grid_for(int64_t n) {
     const int64_t g = (n + NT - 1) / NT;
     return (unsigned)(g < 8192 ? (g > 0 ? g : 1) : 8192);
-}
-
-inline int hip_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
 }
 
 }  // namespace

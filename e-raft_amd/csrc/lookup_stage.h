@@ -16,8 +16,7 @@
 #pragma once
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
-
-typedef unsigned uint2v __attribute__((ext_vector_type(2)));
+#include "split_f16.h"
 
 namespace ecorr {
 
@@ -54,37 +53,20 @@ struct WindowStage : WindowBuf<R, QB, PAIR> {
     float fx[QB][K], wx[QB][K], fy[QB][K], wy[QB][K];
 };
 
-// One coordinate chain (corr.py:41-43, utils.py:11-12, grid_sampler unnormalize): sample o of the
-// axis whose scaled coordinate is cs = coords / 2^lv, on a level side of m1 + 1 pixels.
+// Sample o = 0 .. 2R of an axis: the coordinate chain (ecorr_device.h) at offset o - R.
 template <int R>
 __device__ __forceinline__ void coord_chain(float cs, int o, float m1, float& f, float& wgt) {
-    const float c = __fadd_rn(cs, (float)(o - R));
-    const float v = unnormalize(c, m1, m1 * 0.5f);
-    f = floorf(v);
-    wgt = __fsub_rn(v, f);
+    coord_chain(cs, o - R, m1, f, wgt);
 }
 
 // Phase 0b for one query from its first / last x and y floors: origin and mode word (WindowBuf::org).
 template <int S, bool PAIR = false>
 __device__ __forceinline__ void window_origin(bool valid, float x0, float xl, float y0, float yl, int org[3]) {
-    int md = 2, X0 = 0, Y0 = 0, NX = 0, NY = 0;
-    if (valid) {
-        bool ok = fabsf(x0) < 1.0e7f && fabsf(y0) < 1.0e7f;  // false for NaN / inf / huge
-        // every step of the chain (exact-or-rounded add of the offset, the normalize /
-        // unnormalize roundings by positive factors, floor) is monotone, so the floors are
-        // non-decreasing in the offset and the end points bound the whole window
-        const float dx = xl - x0, dy = yl - y0;   // exact: integers < 2^24
-        ok &= (dx >= 0.0f) & (dx <= (float)(S - 2)) & (dy >= 0.0f) & (dy <= (float)(S - 2));
-        md = ok ? 0 : 1;
-        X0 = ok ? (int)x0 : 0;
-        Y0 = ok ? (int)y0 : 0;
-        // corners span [x0, floor(ix_last) + 1]: monotone round trip, so the last sample bounds it
-        NX = ok ? (int)dx + 2 : 0;
-        NY = ok ? (int)dy + 2 : 0;
-    }
-    org[0] = X0;
-    org[1] = Y0;
-    org[2] = md | (NX << 8) | (NY << 16);
+    WindowFit f = {2, 0, 0, 0, 0};
+    if (valid) f = window_fit(x0, xl, y0, yl, S - 2);
+    org[0] = f.x0;
+    org[1] = f.y0;
+    org[2] = f.md | (f.nx << 8) | (f.ny << 16);
 }
 
 template <int R, int QB, int NTQ, bool PAIR = false>

@@ -28,6 +28,7 @@
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
 #include "lookup_stage.h"
+#include "split_f16.h"
 
 #include <algorithm>
 
@@ -40,9 +41,6 @@ constexpr int NTM = 256;   // threads
 constexpr int OW = 64;     // output channels per wave
 constexpr int OB = 4 * OW; // output channels per pass of the workgroup
 constexpr int KC = 16;     // channels per weight chunk
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // The weight in the GEMM's A-fragment order (pack_weight_kernel, ecorr_conv1x1_pack): for output
 // block ob64 (64 channels = one wave's two 32x32 tiles), channel chunk kc (16 channels) and piece p
@@ -210,8 +208,7 @@ int launch_conv1x1_pack(const float* wt, int O, int C, float* packed, hipStream_
     const int64_t n = conv1x1_packed_floats(O, C) / 4;
     const unsigned grid = (unsigned)std::min<int64_t>((n + NTM - 1) / NTM, 4096);
     hipLaunchKernelGGL(pack_weight_kernel, dim3(grid), dim3(NTM), 0, stream, wt, O, C, packed);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
+    return hip_status();
 }
 
 int launch_lookup_conv(const LookupParams& P, int B, const float* wt, const float* bias, int O, float* out,
@@ -230,8 +227,7 @@ int launch_lookup_conv(const LookupParams& P, int B, const float* wt, const floa
         if (pair) hipLaunchKernelGGL((lookup_conv_kernel<4, true, false>), grid, block, 0, stream, P, wt, bias, O, out);
         else hipLaunchKernelGGL((lookup_conv_kernel<4, false, false>), grid, block, 0, stream, P, wt, bias, O, out);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
+    return hip_status();
 }
 
 }  // namespace ecorr

@@ -47,8 +47,7 @@ int launch_rows_assemble(const float* chunks, int64_t chunk, int world, int B, i
         hipLaunchKernelGGL(rows_assemble_kernel<true>, grid, dim3(RT), 0, stream, chunks, chunk, world, H, W, out);
     else
         hipLaunchKernelGGL(rows_assemble_kernel<false>, grid, dim3(RT), 0, stream, chunks, chunk, world, H, W, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
+    return hip_status();
 }
 
 }  // namespace ecorr

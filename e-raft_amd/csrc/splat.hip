@@ -476,11 +476,6 @@ bool lds_mode(bool flow_mode, int64_t n, int64_t hw) {
     return hw + 4 * n + (flow_mode ? 2 : 3) * n <= kPool;
 }
 
-inline int hip_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
-}
-
 bool band_mode(int64_t n) { return n <= kBandMaxN; }
 
 // bands per item: about 256 workgroups over the chip, at most kBandTargets targets per band

@@ -27,14 +27,13 @@
 // Both are exact integer/byte work (bit-exact).
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "split_f16.h"
 
 namespace ecorr {
 
 namespace {
 
 constexpr int NTU = 256;
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(NTU) void upsample_kernel(const float* __restrict__ flow, const float* __restrict__ mask,
                                                       int H, int W, float* __restrict__ out) {
@@ -123,11 +122,6 @@ __global__ __launch_bounds__(NTU) void png16_decode_kernel(const uint16_t* __res
         flow[2 * q + 1] = ok ? (float)((int)v - 32768) * 0.0078125f : 0.0f;
         valid[q] = ok;
     }
-}
-
-inline int hip_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
 }
 
 inline unsigned grid_for(int64_t n) {

@@ -815,11 +815,6 @@ int plan(int64_t n, uint32_t K, int64_t cells, VoxelWs* w) {
     return ECORR_OK;
 }
 
-inline int hip_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ECORR_OK : ECORR_EHIP - (int)e;
-}
-
 // Workspace of the tiled DSEC path.
 struct VTileWs {
     size_t slot, M, tot, S, pay, norm, part, aord, aords, total;

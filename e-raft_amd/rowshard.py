@@ -25,7 +25,7 @@ import torch.distributed as dist
 
 from . import _lib
 from ._lib import _no_grad_inputs, _require_device_f32
-from .layout import formats, untile
+from .layout import levels_of
 
 
 def row_partition(H, world):
@@ -186,11 +186,8 @@ class RowShardedCorrBlock:
     def corr_pyramid(self):
         """This rank's levels in the reference layout [B*rows_r*W, 1, h_i, w_i] (a copy)."""
         if self._levels_cache is None:
-            rows = self._shape[0] * self.q_count
-            ntx = formats(self._shape[2], self._shape[3], self.num_levels)
-            self._levels_cache = [
-                untile(self._pyramid[self._off[i]:self._off[i + 1]], rows, self._h[i], self._w[i], ntx[i], i)
-                for i in range(self.num_levels)]
+            self._levels_cache = levels_of(self._pyramid, self._shape[0] * self.q_count, self._shape[2],
+                                           self._shape[3], self.num_levels)
         return self._levels_cache
 
     def _local_coords(self, coords_rows):
@@ -206,12 +203,8 @@ class RowShardedCorrBlock:
 
     def _lookup_into(self, coords_rows, out):
         B, _, H, W = self._shape
-        with _lib.on_device(self._device):
-            _lib.check(_lib.lib().ecorr_lookup(
-                self._pyramid.data_ptr(), coords_rows.data_ptr(), B, H, W, self.q_count,
-                self.num_levels, self.radius, out.data_ptr(), _lib.stream_of(out)),
-                "RowShardedCorrBlock lookup")
-        return out
+        return _lib.lookup(self._pyramid, coords_rows, (B, H, W), self.q_count, self.num_levels, self.radius, out,
+                           "RowShardedCorrBlock")
 
     def lookup_local(self, coords_rows):
         """Lookup for this rank's query rows: coords [B, 2, rows_r, W] -> [B, C, rows_r, W]."""

@@ -303,7 +303,9 @@ PATCHES["s16_rd8"] = [("build.hip", """#pragma unroll
         }""")]
 # round 6, timing only (what bounds the split conv's instruction floor?): the split VALU replaced
 # by one conversion per value (lo = 0), and the A-fragment LDS reads replaced by register values
-PATCHES["cv_nosplit"] = [("conv.hip", """        const float x = v[j] * s;
+# (split_f16 is shared, split_f16.h: the cv_nosplit / cv_fmix / cv_mixasm libraries change the
+# build's operand pass with it -- time only the conv with them)
+PATCHES["cv_nosplit"] = [("split_f16.h", """        const float x = v[j] * s;
         const _Float16 h = (_Float16)x;
         hi[j] = h;
         lo[j] = (_Float16)(x - (float)h);""", """        hi[j] = (_Float16)v[j];
@@ -318,10 +320,10 @@ PATCHES["cv_nolds"] = [("conv.hip", """            ah[i] = *reinterpret_cast<con
                 al[s] = bh * (_Float16)(i + 4);""")]
 # round 6: the split's lo half as one fused op, f16(fma(hi, -1, x)) -- v_fma_mix (hi extended from f16
 # in the fma, one rounding to f16: bitwise (_Float16)(x - (float)hi), x - hi being exact)
-PATCHES["cv_fmix"] = [("conv.hip", """        lo[j] = (_Float16)(x - (float)h);""", """        lo[j] = (_Float16)__builtin_fmaf((float)h, -1.0f, x);""")]
+PATCHES["cv_fmix"] = [("split_f16.h", """        lo[j] = (_Float16)(x - (float)h);""", """        lo[j] = (_Float16)__builtin_fmaf((float)h, -1.0f, x);""")]
 # round 6: the split with v_fma_mixlo/hi_f16 (inline asm; the compiler turns fma(hi, -1, x) back into
 # sub + converts): lo pair = f16(x0 - hi0), f16(x1 - hi1) from the packed hi register, 2 ops per pair
-PATCHES["cv_mixasm"] = [("conv.hip", """__device__ __forceinline__ void split8(const float (&v)[8], float s, halfx8& hi, halfx8& lo) {
+PATCHES["cv_mixasm"] = [("split_f16.h", """__device__ __forceinline__ void split_f16(const float (&v)[8], float s, halfx8& hi, halfx8& lo) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float x = v[j] * s;
@@ -329,7 +331,7 @@ PATCHES["cv_mixasm"] = [("conv.hip", """__device__ __forceinline__ void split8(c
         hi[j] = h;
         lo[j] = (_Float16)(x - (float)h);
     }
-}""", """__device__ __forceinline__ void split8(const float (&v)[8], float s, halfx8& hi, halfx8& lo) {
+}""", """__device__ __forceinline__ void split_f16(const float (&v)[8], float s, halfx8& hi, halfx8& lo) {
     typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
@@ -762,10 +764,11 @@ PATCHES["pk_nostore"] = [("build.hip", _PK_ST, "        if (h0[0] == (_Float16)1
 PATCHES["pk_noload"] = [("build.hip", "                v[i][kk] = (pix >= 0 && k < D) ? px[(int64_t)k * N] : 0.f;",
                          "                v[i][kk] = (pix >= 0 && k < D) ? (float)(pix + k) : 0.f;")]
 # operand pass (timing + accuracy probe, not bitwise): the split's lo halves rounded down to 8 / 6
-# significant bits (fewer toggling multiplier bits in the lo.hi / hi.lo MFMAs of a power-limited GEMM)
-PATCHES["lo8"] = [("build.hip", "        lo[j] = (_Float16)(x - (float)h);",
+# significant bits (fewer toggling multiplier bits in the lo.hi / hi.lo MFMAs of a power-limited GEMM);
+# split_f16 is shared (split_f16.h): the split convc1's halves are rounded down with the build's
+PATCHES["lo8"] = [("split_f16.h", "        lo[j] = (_Float16)(x - (float)h);",
                    "        lo[j] = (_Float16)__uint_as_float(__float_as_uint(x - (float)h) & 0xFFFF0000u);")]
-PATCHES["lo6"] = [("build.hip", "        lo[j] = (_Float16)(x - (float)h);",
+PATCHES["lo6"] = [("split_f16.h", "        lo[j] = (_Float16)(x - (float)h);",
                    "        lo[j] = (_Float16)__uint_as_float(__float_as_uint(x - (float)h) & 0xFFFC0000u);")]
 # voxel count blocks (bitwise): 512 threads x 8 events (245 blocks at 1M events) / 1024 x 4 (245)
 PATCHES["vx_cnt512"] = [("voxel.hip", "constexpr int VB_CNT = 1024, VB_EPB = 8 * VB_CNT;", "constexpr int VB_CNT = 512, VB_EPB = 8 * VB_CNT;")]
