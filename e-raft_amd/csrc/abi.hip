@@ -26,12 +26,12 @@ int pyramid_geometry(int64_t rows, int H, int W, int levels, PyrGeom* g) {
         g->h[i] = hh;
         g->w[i] = ww;
         int64_t nrows = rows;
-        if (i >= 1 && i <= 3) {   // interleaved (ecorr_device.h pix_off): 2 x 4 / 2 x 4 / 1 x 2 blocks
+        if (level_ilv(i)) {   // ecorr_device.h: 2 x 4 / 2 x 4 / 1 x 2 blocks
             const int bh = 1 << ilv_sy(i), bw = 1 << ilv_sx(i);
             const int nby = (hh + bh - 1) / bh, nbx = (ww + bw - 1) / bw;
             g->ntx[i] = -nbx;
             g->nty[i] = nby;
-            g->sz[i] = (int64_t)nby * nbx * bh * bw;
+            g->sz[i] = (int64_t)nby * nbx * ilv_bsz(i);
             nrows = (rows + kGroup - 1) / kGroup * kGroup;
         } else if (level_compact(i, hh, ww)) {
             g->ntx[i] = 0;
@@ -180,13 +180,8 @@ int lookup_params(const float* pyramid, const float* coords, int B, int H, int W
     PyrGeom g;
     const int st = pyramid_geometry((int64_t)B * q_count, H, W, levels, &g);
     if (st != ECORR_OK) return st;
-    for (int i = 0; i < levels; ++i) {
-        P->lvl[i] = pyramid + g.off[i];
-        P->lh[i] = g.h[i];
-        P->lw[i] = g.w[i];
-        P->lntx[i] = g.ntx[i];
-        P->lsz[i] = (int)g.sz[i];
-    }
+    if (g.sz[0] > 0x7fffffff) return ECORR_EINVAL;   // the lookup kernels' offsets inside a query image are 32-bit
+    level_table<const float>(g, pyramid, P);
     P->coords = coords;
     P->out = out;
     P->H = H;
@@ -221,18 +216,16 @@ ECORR_EXPORT int ecorr_lookup_qmax(const float* pyramid, const float* coords, in
 
 namespace {
 
-int grad_params(float* grad_pyramid, int B, int H, int W, int q_count, int levels, PyrGeom* g, LookupGradParams* P) {
-    if (!grad_pyramid || B <= 0 || B > 65535) return ECORR_EINVAL;
+// radius: the lookup's (the build backward has none: 0)
+int grad_params(float* grad_pyramid, int B, int H, int W, int q_count, int levels, int radius, PyrGeom* g,
+                LookupGradParams* P) {
+    if (!grad_pyramid || B <= 0) return ECORR_EINVAL;
     if (!q_count_ok(H, W, q_count)) return ECORR_EINVAL;
+    if (radius < 0 || radius > 32) return ECORR_ERADIUS;
+    if (B > 65535) return ECORR_EINVAL;
     const int st = pyramid_geometry((int64_t)B * q_count, H, W, levels, g);
     if (st != ECORR_OK) return st;
-    for (int i = 0; i < levels; ++i) {
-        P->lvl[i] = grad_pyramid + g->off[i];
-        P->lh[i] = g->h[i];
-        P->lw[i] = g->w[i];
-        P->lntx[i] = g->ntx[i];
-        P->lsz[i] = g->sz[i];
-    }
+    level_table<float>(*g, grad_pyramid, P);
     P->q_count = q_count;
     P->levels = levels;
     return ECORR_OK;
@@ -242,12 +235,10 @@ int grad_params(float* grad_pyramid, int B, int H, int W, int q_count, int level
 
 ECORR_EXPORT int ecorr_lookup_backward(const float* grad_out, const float* coords, int B, int H, int W, int q_count,
                                        int levels, int radius, float* grad_pyramid, void* stream) {
-    if (!grad_out || !coords || !grad_pyramid || B <= 0) return ECORR_EINVAL;
-    if (!q_count_ok(H, W, q_count)) return ECORR_EINVAL;
-    if (radius < 0 || radius > 32) return ECORR_ERADIUS;
+    if (!grad_out || !coords) return ECORR_EINVAL;
     PyrGeom g;
     LookupGradParams P{};
-    const int st = grad_params(grad_pyramid, B, H, W, q_count, levels, &g, &P);
+    const int st = grad_params(grad_pyramid, B, H, W, q_count, levels, radius, &g, &P);
     if (st != ECORR_OK) return st;
     P.grad_out = grad_out;
     P.coords = coords;
@@ -262,7 +253,7 @@ ECORR_EXPORT int ecorr_build_backward(float* grad_pyramid, const float* fmap1, c
     if (!grad_pyramid || !fmap1 || !fmap2 || B <= 0 || D <= 0) return ECORR_EINVAL;
     PyrGeom g;
     LookupGradParams L{};
-    const int st = grad_params(grad_pyramid, B, H, W, q_count, levels, &g, &L);
+    const int st = grad_params(grad_pyramid, B, H, W, q_count, levels, 0, &g, &L);
     if (st != ECORR_OK) return st;
     if (g.sz[0] > 0x7fffffff) return ECORR_EINVAL;
     BuildGradParams P{};

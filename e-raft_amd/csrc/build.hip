@@ -104,8 +104,8 @@ constexpr int kGM16 = 10;   // build_split16_kernel's group bound (balanced); th
 // in a tile's padding are written and never read), interleaved (ntx < 0; likewise the block) or
 // compact row-major (range-checked).
 __device__ __forceinline__ float* level_px(const BuildParams& P, int L, int64_t row_img, int r, int c) {
-    if (P.lntx[L] < 0) {   // interleaved (levels 2, 3): the block must exist
-        if ((r >> ilv_sy(L)) >= P.lnty[L] || (c >> ilv_sx(L)) >= -P.lntx[L]) return nullptr;
+    if (P.lntx[L] < 0) {   // interleaved: the block must exist
+        if (!ilv_cell_in(r, c, L, P.lnty[L], -P.lntx[L])) return nullptr;
         return P.lvl[L] + pix_off(row_img, r, c, L, P.lntx[L], P.lw[L], P.lsz[L]);
     }
     float* img = P.lvl[L] + row_img * P.lsz[L];
@@ -115,6 +115,17 @@ __device__ __forceinline__ float* level_px(const BuildParams& P, int L, int64_t 
     }
     if (r >= P.lh[L] || c >= P.lw[L]) return nullptr;
     return img + (int64_t)r * P.lw[L] + c;
+}
+
+// Buffer descriptor over the slab of fused level lv that holds the query images [rows0, rows0 + nq)
+// (ecorr_device.h slab_first / slab_bytes): its range check is the query bound.  lv >= 1: the fused
+// levels that are interleaved.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t level_rsrc(const BuildParams& P, int lv, int64_t rows0, int nq) {
+    if (lv >= 1)
+        return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + slab_first(true, rows0, P.lsz[lv]), 0,
+                                                 (int)slab_bytes(true, rows0, nq, P.lsz[lv]), 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + slab_first(false, rows0, P.lsz[lv]), 0,
+                                             (int)slab_bytes(false, rows0, nq, P.lsz[lv]), 0x00020000);
 }
 
 // ============================================================================================
@@ -207,16 +218,9 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
     const int L = P.fused_levels;
     const int64_t rows0 = (int64_t)b * P.q_count + q0;   // the block's first query image
     const int nq = min(SQ, P.q_count - q0);
-    // per-level descriptors over the block's query images (range check = query bound); levels 2-3
-    // (interleaved): over the 64-row groups the block's rows touch, from group g0 = rows0 / 64
-    const int64_t g0 = rows0 >> 6;
-    auto rsrc_of = [&](int lv) {
-        if (lv >= 1)
-            return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + g0 * kGroup * P.lsz[lv], 0,
-                                                     (int)((((rows0 + nq - 1) >> 6) - g0 + 1) * kGroup * P.lsz[lv] * 4),
-                                                     0x00020000);
-        return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + rows0 * P.lsz[lv], 0, (int)(nq * P.lsz[lv] * 4), 0x00020000);
-    };
+    // per-level descriptors over the block's query images (level_rsrc); interleaved levels: over
+    // the 64-row groups the block's rows touch, from group g0
+    const int64_t g0 = slab_g0(rows0);
     // read the transposed segments back and store them: line byte offset lo (+ the query image)
     auto store_lines = [&](const char* xp, __amdgpu_buffer_rsrc_t rs, int64_t lsz, int ql, int lo, bool ok) {
         floatx4 pc[4];
@@ -235,13 +239,9 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
     // blocks outside the level are dropped (padding cells of a block are written, never read).
     auto store_px = [&](__amdgpu_buffer_rsrc_t rs, int lv, int qloc, int r, int c, auto val) {
         constexpr int N = sizeof(val) / 4;
-        const int sy = ilv_sy(lv), sx = ilv_sx(lv);
-        const int by = r >> sy, bx = c >> sx;
-        const bool in = qloc < nq && by < P.lnty[lv] && bx < -P.lntx[lv];
-        const int64_t R = rows0 + qloc;
-        const int off = (int)((((R >> 6) - g0) * kGroup * P.lsz[lv] +
-                               ((int64_t)(by * -P.lntx[lv] + bx) * kGroup + (R & (kGroup - 1))) * (1 << (sy + sx)) +
-                               ((r & ((1 << sy) - 1)) << sx)) * 4);
+        const bool in = qloc < nq && ilv_cell_in(r, c, lv, P.lnty[lv], -P.lntx[lv]);
+        // row term + cell term, each in 32 bits (summed in 64 bits the epilogue grows by ~200 instructions)
+        const int off = ((int)ilv_row_off(rows0 + qloc, g0, lv, P.lsz[lv]) + (int)ilv_cell_off(r, c, lv, -P.lntx[lv])) * 4;
         if constexpr (N == 4)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, val), rs, in ? off : SOOB, 0, ST_L01);
         else
@@ -261,10 +261,10 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
         }
         fast_scale = __all(ok);
     }
-    const __amdgpu_buffer_rsrc_t r0 = rsrc_of(0);
-    const __amdgpu_buffer_rsrc_t r1 = rsrc_of(L > 1 ? 1 : 0);
-    const __amdgpu_buffer_rsrc_t r2 = rsrc_of(L > 2 ? 2 : 0);
-    const __amdgpu_buffer_rsrc_t r3 = rsrc_of(L > 3 ? 3 : 0);
+    const __amdgpu_buffer_rsrc_t r0 = level_rsrc(P, 0, rows0, nq);
+    const __amdgpu_buffer_rsrc_t r1 = level_rsrc(P, L > 1 ? 1 : 0, rows0, nq);
+    const __amdgpu_buffer_rsrc_t r2 = level_rsrc(P, L > 2 ? 2 : 0, rows0, nq);
+    const __amdgpu_buffer_rsrc_t r3 = level_rsrc(P, L > 3 ? 3 : 0, rows0, nq);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int ql = qw + 32 * i;          // first block-local query of this tile row
@@ -321,7 +321,7 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
                         floatx4{v[jl][g4][0], v[jl][g4][1], v[jl][g4][2], v[jl][g4][3]};
                 const int tr = (tc.ty0 >> 2) + (tc.band ? 0 : (j & 1));
                 const int tcl = (tc.tx0 >> 3) + (tc.band ? j : (j >> 1));
-                store_lines(xp, r0, P.lsz[0], ql, ((tr * P.lntx[0] + tcl) * kTile) * 4 + 64 * arow,
+                store_lines(xp, r0, P.lsz[0], ql, tile_base(tr, tcl, P.lntx[0]) * 4 + 64 * arow,
                             tr < P.lnty[0] && tcl < P.lntx[0]);
             }
             if (L < 2) continue;
@@ -695,18 +695,10 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
     const int L = P.fused_levels;
     const int64_t rows0 = (int64_t)b * P.q_count + q0;   // the block's first query image
     const int nq = min(SQ, P.q_count - q0);
-    const int64_t g0 = rows0 >> 6;
-    auto rsrc_of = [&](int lv) {
-        if (lv >= 1)
-            return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + g0 * kGroup * P.lsz[lv], 0,
-                                                     (int)((((rows0 + nq - 1) >> 6) - g0 + 1) * kGroup * P.lsz[lv] * 4),
-                                                     0x00020000);
-        return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + rows0 * P.lsz[lv], 0, (int)(nq * P.lsz[lv] * 4), 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t r0 = rsrc_of(0);
-    const __amdgpu_buffer_rsrc_t r1 = rsrc_of(L > 1 ? 1 : 0);
-    const __amdgpu_buffer_rsrc_t r2 = rsrc_of(L > 2 ? 2 : 0);
-    const __amdgpu_buffer_rsrc_t r3 = rsrc_of(L > 3 ? 3 : 0);
+    const __amdgpu_buffer_rsrc_t r0 = level_rsrc(P, 0, rows0, nq);
+    const __amdgpu_buffer_rsrc_t r1 = level_rsrc(P, L > 1 ? 1 : 0, rows0, nq);
+    const __amdgpu_buffer_rsrc_t r2 = level_rsrc(P, L > 2 ? 2 : 0, rows0, nq);
+    const __amdgpu_buffer_rsrc_t r3 = level_rsrc(P, L > 3 ? 3 : 0, rows0, nq);
     // level-0 line (tile row, tile col) of quadrant k of the n-tile
     auto line_tr = [&](int k) { return (tc.ty0 >> 2) + (tc.band ? 0 : (k & 1)); };
     auto line_tc = [&](int k) { return (tc.tx0 >> 3) + (tc.band ? k : (k >> 1)); };
@@ -729,19 +721,16 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
     {
         const int lk = jl >> 1, ltr = line_tr(lk), ltc = line_tc(lk);
         l0ok = ltr < P.lnty[0] && ltc < P.lntx[0];
-        l0off = (qw + (jl & 1 ? 8 : 0)) * l0stride + ((ltr * P.lntx[0] + ltc) * kTile) * 4 + 16 * pc;
+        l0off = (qw + (jl & 1 ? 8 : 0)) * l0stride + tile_base(ltr, ltc, P.lntx[0]) * 4 + 16 * pc;
     }
     const int l0q = qw + (jl & 1 ? 8 : 0);              // query row of store s = 0 (block-local)
-    // Interleaved levels 1-3 ([group][block][row][bh][bw], ecorr_device.h): a piece of query row R
-    // (block-local qloc) at byte (grp G + rin bsz + blkoff) 4, grp = (R >> 6) - g0, rin = R & 63,
-    // G = kGroup lsz floats per group, bsz = block floats; blkoff = block index kGroup bsz + the
-    // piece's in-block offset (the lane's; -1 = outside the level)
+    // Interleaved levels 1-3 (ecorr_device.h): a piece of query row R at byte (rowoff + blkoff) 4 of
+    // the block's slab; rowoff = ilv_row_off of rr = R - 64 g0 (a slab is below 2^31 bytes: 32-bit),
+    // blkoff = ilv_cell_off of the piece's first pixel (the lane's; -1 = outside the level)
     const int rl0 = (int)(rows0 & (kGroup - 1));          // row-in-group of the block's first query
     auto ilv_blkoff = [&](int lv, int r, int c) {          // level pixel (r, c) -> blkoff, or -1
-        const int sy = ilv_sy(lv), sx = ilv_sx(lv);
-        const int by = r >> sy, bx = c >> sx;
-        if (by >= P.lnty[lv] || bx >= -P.lntx[lv]) return -1;
-        return (by * -P.lntx[lv] + bx) * kGroup * (1 << (sy + sx)) + ((r & ((1 << sy) - 1)) << sx) + (c & ((1 << sx) - 1));
+        if (!ilv_cell_in(r, c, lv, P.lnty[lv], -P.lntx[lv])) return -1;
+        return (int)ilv_cell_off(r, c, lv, -P.lntx[lv]);
     };
     // level 1: after the row swap, lane kb holds block row kb & 1 of quadrants kb & ~1 (x) and kb | 1 (y)
     const int b1x = L > 1 ? ilv_blkoff(1, 2 * line_tr(kb & ~1) + (kb & 1), 4 * line_tc(kb & ~1)) : -1;
@@ -750,8 +739,7 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
     const int b2 = L > 2 ? ilv_blkoff(2, line_tr(kb), 2 * line_tc(kb)) : -1;
     // level 3 (regular tiles, stored by the kb = 0 lanes): the tile's 1 x 2 at (ty0 / 8, tx0 / 8)
     const int b3 = (L > 3 && !tc.band && kb == 0) ? ilv_blkoff(3, tc.ty0 >> 3, tc.tx0 >> 3) : -1;
-    const int G1 = kGroup * (int)P.lsz[L > 1 ? 1 : 0], G2 = kGroup * (int)P.lsz[L > 2 ? 2 : 0],
-              G3 = kGroup * (int)P.lsz[L > 3 ? 3 : 0];
+    auto rowoff = [&](int lv, int rr) { return (int)ilv_row_off(rr, 0, lv, P.lsz[L > lv ? lv : 0]); };   // rr: row from the slab's first group
     auto st4 = [&](__amdgpu_buffer_rsrc_t rs, int off, bool ok, floatx4 v) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, ok ? off : SOOB, 0, ST_L01);
     };
@@ -768,8 +756,8 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
     constexpr int FOOB = 0x70000000;   // + any uniform term stays beyond every slab, below 2^31
     const int qwu = __builtin_amdgcn_readfirstlane(qw);   // wave-uniform (qw = 64 wave)
     const int v0 = l0ok ? l0off - qw * l0stride : FOOB;   // + (qw + 16 qg + s) l0stride
-    const int v1x = b1x >= 0 ? (qn * 8 + b1x) * 4 : FOOB, v1y = b1y >= 0 ? (qn * 8 + b1y) * 4 : FOOB;
-    const int v2 = b2 >= 0 ? (qn * 8 + b2) * 4 : FOOB, v3 = b3 >= 0 ? (qn * 2 + b3) * 4 : FOOB;
+    const int v1x = b1x >= 0 ? (rowoff(1, qn) + b1x) * 4 : FOOB, v1y = b1y >= 0 ? (rowoff(1, qn) + b1y) * 4 : FOOB;
+    const int v2 = b2 >= 0 ? (rowoff(2, qn) + b2) * 4 : FOOB, v3 = b3 >= 0 ? (rowoff(3, qn) + b3) * 4 : FOOB;
     const int grpw = qwu >> 6;   // FULL: the wave's interleaved group (block-relative)
     auto fst4 = [&](__amdgpu_buffer_rsrc_t rs, int voff, int uoff, floatx4 v) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, voff + uoff, 0, ST_L01);
@@ -836,7 +824,6 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
         if (L < 2) continue;
         // this lane's query row in its interleaved group
         const int rr = rl0 + ql + qn;
-        const int grp = rr >> 6, rin = rr & (kGroup - 1);
         const bool qok = ql + qn < nq;
         // level 1: the quadrant's 2 x 4 block, l1[r][c] from quadrant rows 2r, 2r + 1, cols 2c, 2c + 1
         auto q0v = [&](int yy, int xx) { return v[2 * yy + (xx >> 2)][xx & 3]; };
@@ -863,18 +850,18 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
                 y[c] = __uint_as_float(sw[1]);
             }
             if (FULL) {
-                fst4(r1, v1x, (grpw * G1 + 16 * qg * 8) * 4, floatx4{x[0], x[1], x[2], x[3]});
-                fst4(r1, v1y, (grpw * G1 + 16 * qg * 8) * 4, floatx4{y[0], y[1], y[2], y[3]});
+                fst4(r1, v1x, rowoff(1, (grpw << 6) + 16 * qg) * 4, floatx4{x[0], x[1], x[2], x[3]});
+                fst4(r1, v1y, rowoff(1, (grpw << 6) + 16 * qg) * 4, floatx4{y[0], y[1], y[2], y[3]});
             } else {
-                const int base1 = grp * G1 + rin * 8;
+                const int base1 = rowoff(1, rr);
                 st4(r1, (base1 + b1x) * 4, qok && b1x >= 0, floatx4{x[0], x[1], x[2], x[3]});
                 st4(r1, (base1 + b1y) * 4, qok && b1y >= 0, floatx4{y[0], y[1], y[2], y[3]});
             }
         }
         if (L < 3) continue;
         // level 2: 4 lanes x 8 B = one query's 2 x 4 block (band: half of two)
-        if (FULL) fst2(r2, v2, (grpw * G2 + 16 * qg * 8) * 4, floatx2{l2[0], l2[1]});
-        else st2(r2, (grp * G2 + rin * 8 + b2) * 4, qok && b2 >= 0, floatx2{l2[0], l2[1]});
+        if (FULL) fst2(r2, v2, rowoff(2, (grpw << 6) + 16 * qg) * 4, floatx2{l2[0], l2[1]});
+        else st2(r2, (rowoff(2, rr) + b2) * 4, qok && b2 >= 0, floatx2{l2[0], l2[1]});
         if (L < 4 || tc.band) continue;
         // level 3 (regular tiles): pixel kb >> 1 of the tile's 1 x 2 from the 2 x 2 level-2 pixels of
         // lanes kb (row 0, kb even) and kb + 1 (row 1), brought over by a row swap; lane kb = 0 takes
@@ -883,8 +870,8 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
         const auto o1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(l2[1]), __float_as_uint(l2[1]), false, false);
         const float p3 = pool4(l2[0], l2[1], __uint_as_float(o0[1]), __uint_as_float(o1[1]));
         const auto p3s = __builtin_amdgcn_permlane32_swap(__float_as_uint(p3), __float_as_uint(p3), false, false);
-        if (FULL) fst2(r3, v3, (grpw * G3 + 16 * qg * 2) * 4, floatx2{p3, __uint_as_float(p3s[1])});
-        else st2(r3, (grp * G3 + rin * 2 + b3) * 4, qok && b3 >= 0, floatx2{p3, __uint_as_float(p3s[1])});
+        if (FULL) fst2(r3, v3, rowoff(3, (grpw << 6) + 16 * qg) * 4, floatx2{p3, __uint_as_float(p3s[1])});
+        else st2(r3, (rowoff(3, rr) + b3) * 4, qok && b3 >= 0, floatx2{p3, __uint_as_float(p3s[1])});
     }
 }
 
@@ -1412,7 +1399,7 @@ __device__ __forceinline__ void epilogue(const BuildParams& P, const TileCoord& 
             if (m < mvalid && tr < nty && tcc < ntx) {
                 const floatx4 v = *reinterpret_cast<const floatx4*>(
                     Cs + m * CS + (trl * 4 + (j >> 1)) * TBW + tcl * 8 + (j & 1) * 4);
-                st_nt(reinterpret_cast<floatx4*>(P.lvl[0] + (row0 + m) * P.lsz[0] + (tr * ntx + tcc) * kTile + 4 * j), v);
+                st_nt(reinterpret_cast<floatx4*>(P.lvl[0] + (row0 + m) * P.lsz[0] + tile_base(tr, tcc, ntx) + 4 * j), v);
             }
         }
     }
@@ -1501,7 +1488,7 @@ __device__ __forceinline__ void epilogue_band(const BuildParams& P, const TileCo
             const int tcl = rem >> 3, j = rem & 7;
             if (m < mvalid && tc0 + tcl < ntx) {
                 const floatx4 v = *reinterpret_cast<const floatx4*>(Cs + m * CS + (j >> 1) * 32 + tcl * 8 + (j & 1) * 4);
-                st_nt(reinterpret_cast<floatx4*>(P.lvl[0] + (row0 + m) * P.lsz[0] + (tr * ntx + tc0 + tcl) * kTile + 4 * j), v);
+                st_nt(reinterpret_cast<floatx4*>(P.lvl[0] + (row0 + m) * P.lsz[0] + tile_base(tr, tc0 + tcl, ntx) + 4 * j), v);
             }
         }
     }
@@ -1817,15 +1804,7 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
     const int levels = g.levels;
     P.fused_levels = levels < 4 ? levels : 4;
     tile_counts(P);
-    for (int i = 0; i < 4; ++i) {
-        const bool on = i < levels;
-        P.lvl[i] = on ? pyramid + g.off[i] : nullptr;
-        P.lh[i] = on ? g.h[i] : 0;
-        P.lw[i] = on ? g.w[i] : 0;
-        P.lntx[i] = on ? g.ntx[i] : 0;
-        P.lnty[i] = on ? g.nty[i] : 0;
-        P.lsz[i] = on ? g.sz[i] : 0;
-    }
+    level_table<float>(g, pyramid, &P);   // zeros past the last level: the kernels index levels < 4 unguarded
     if ((uintptr_t)pyramid % 16 != 0) return ECORR_EINVAL;   // tile stores are 16-byte vectors
     if (P.ws) {
         // split build: one 128-query tile's panels (dc * 8 KB, the buffer range of the kernel's

@@ -17,6 +17,9 @@ constexpr int kWave = 64;
 // Pyramid level storage (include/ecorr.h): each query's level image [h][w] is stored as
 // row-major 4 x 8-float tiles (128 B = one L2 line); ntx = padded width / 8 tiles per tile row.
 constexpr int kTileH = 4, kTileW = 8, kTile = kTileH * kTileW;
+// float offset of tile (tr, tc)'s line in a query image
+__host__ __device__ __forceinline__ int tile_base(int tr, int tc, int ntx) { return (tr * ntx + tc) * kTile; }
+// pixel (y, x) = tile_base(y >> 2, x >> 3, ntx) + in-tile offset, spelled out (the call reorders kernels)
 __host__ __device__ __forceinline__ int tiled_off(int y, int x, int ntx) {
     return (((y >> 2) * ntx + (x >> 3)) << 5) + ((y & 3) << 3) + (x & 7);
 }
@@ -29,11 +32,13 @@ __host__ __device__ __forceinline__ void tiled_cell_yx(int c, int ntx, int& y, i
 __host__ __device__ __forceinline__ int pad_h(int h) { return (h + kTileH - 1) & ~(kTileH - 1); }
 __host__ __device__ __forceinline__ int pad_w(int w) { return (w + kTileW - 1) & ~(kTileW - 1); }
 
-// Levels >= 4 (levels 2-3 are interleaved, below) whose tile padding would exceed half the image
-// are stored compact row-major instead: the window covers most of such an image, so the padding
-// would only add lines to every lookup's read footprint.
+// Levels 1-3 are interleaved (below), so only level 0 and levels >= 4 are tiled, and only levels
+// >= 4 can be compact: those whose tile padding would exceed half the image are stored row-major
+// instead (the window covers most of such an image, so the padding would only add lines to every
+// lookup's read footprint).
+__host__ __device__ __forceinline__ bool level_ilv(int level) { return level >= 1 && level <= 3; }
 __host__ __device__ __forceinline__ bool level_compact(int level, int h, int w) {
-    return level >= 2 && 2 * pad_h(h) * pad_w(w) > 3 * h * w;
+    return level >= 4 && 2 * pad_h(h) * pad_w(w) > 3 * h * w;
 }
 
 // Offset of pixel (y, x) in one query image: tiled (ntx = tiles per tile row > 0) or row-major
@@ -51,15 +56,45 @@ __host__ __device__ __forceinline__ int level_off(int y, int x, int ntx, int w) 
 constexpr int kGroup = ECORR_ROW_GROUP;
 __host__ __device__ __forceinline__ int ilv_sy(int lv) { return lv == 3 ? 0 : 1; }   // log2 block height
 __host__ __device__ __forceinline__ int ilv_sx(int lv) { return lv == 3 ? 1 : 2; }   // log2 block width
+__host__ __device__ __forceinline__ int ilv_bsz(int lv) { return 1 << (ilv_sy(lv) + ilv_sx(lv)); }   // block floats
+// The format's one definition: the float offset of pixel (y, x) of query row R in a level of nbx
+// blocks per block row and sz floats per query image, from the first float of 64-row group g0.  It
+// is the sum of a row term (this function at pixel (0, 0)) and a cell term (at row 0, sz 0), which
+// the build epilogues take apart: the cell term hoisted out of their query loops.
+__host__ __device__ __forceinline__ int64_t ilv_pix_off(int64_t R, int64_t g0, int y, int x, int lv, int nbx,
+                                                        int64_t sz) {
+    const int sy = ilv_sy(lv), sx = ilv_sx(lv);
+    return ((R >> 6) - g0) * (kGroup * sz) +
+           ((int64_t)((y >> sy) * nbx + (x >> sx)) * kGroup + (R & (kGroup - 1))) * (1 << (sy + sx)) +
+           ((y & ((1 << sy) - 1)) << sx) + (x & ((1 << sx) - 1));
+}
+__host__ __device__ __forceinline__ int64_t ilv_row_off(int64_t R, int64_t g0, int lv, int64_t sz) {
+    return ilv_pix_off(R, g0, 0, 0, lv, 0, sz);
+}
+__host__ __device__ __forceinline__ int64_t ilv_cell_off(int y, int x, int lv, int nbx) {
+    return ilv_pix_off(0, 0, y, x, lv, nbx, 0);
+}
+// whether pixel (y, x)'s block exists in a level of nby x nbx blocks
+__host__ __device__ __forceinline__ bool ilv_cell_in(int y, int x, int lv, int nby, int nbx) {
+    return (y >> ilv_sy(lv)) < nby && (x >> ilv_sx(lv)) < nbx;
+}
 
 // Float offset of pixel (y, x) of query row R (0 .. B*q_count - 1) from the level's base, any
 // format; sz = floats per query image (an interleaved group spans kGroup * sz floats).
 __host__ __device__ __forceinline__ int64_t pix_off(int64_t R, int y, int x, int lv, int ntx, int w, int64_t sz) {
     if (ntx >= 0) return R * sz + level_off(y, x, ntx, w);
-    const int sy = ilv_sy(lv), sx = ilv_sx(lv);
-    return (R >> 6) * (kGroup * sz) +
-           ((int64_t)((y >> sy) * -ntx + (x >> sx)) * kGroup + (R & (kGroup - 1))) * (1 << (sy + sx)) +
-           ((y & ((1 << sy) - 1)) << sx) + (x & ((1 << sx) - 1));
+    return ilv_pix_off(R, 0, y, x, lv, -ntx, sz);
+}
+
+// The slab of a level that holds query rows [R0, R0 + nq), any format (ilv: interleaved), which a
+// buffer descriptor over those rows spans: its first float from the level's base and its bytes --
+// the 64-row groups the rows touch, from group g0 (which ilv_pix_off counts from), else the nq images.
+__host__ __device__ __forceinline__ int64_t slab_g0(int64_t R0) { return R0 >> 6; }
+__host__ __device__ __forceinline__ int64_t slab_first(bool ilv, int64_t R0, int64_t sz) {
+    return ilv ? slab_g0(R0) * kGroup * sz : R0 * sz;
+}
+__host__ __device__ __forceinline__ int64_t slab_bytes(bool ilv, int64_t R0, int nq, int64_t sz) {
+    return (ilv ? (((R0 + nq - 1) >> 6) - slab_g0(R0) + 1) * kGroup * sz : nq * sz) * 4;
 }
 
 // model/utils.py:11-12 then ATen grid_sampler unnormalize (align_corners=True):

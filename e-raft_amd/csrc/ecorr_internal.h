@@ -26,7 +26,34 @@ struct PyrGeom {
 
 int pyramid_geometry(int64_t rows, int H, int W, int levels, PyrGeom* g);
 
-struct BuildParams {
+// The per-level table the kernels read: a pyramid's (or a gradient pyramid's) levels in the storage
+// of ecorr_device.h.  The parameter structs below start with it; level_table() fills it.  F: float
+// where the kernels write the levels (the build, the backward), const float where they only read.
+// One size for all three: the build indexes levels < 4 only and the lookups never read lnty.
+template <typename F>
+struct LevelTable {
+    F* lvl[ECORR_MAX_LEVELS];                          // first float of each level (null past the last)
+    int lh[ECORR_MAX_LEVELS], lw[ECORR_MAX_LEVELS];   // true level sizes
+    int lntx[ECORR_MAX_LEVELS];                        // > 0 tiles per tile row, < 0 -blocks per block row
+                                                       // (interleaved), 0 compact row-major
+    int lnty[ECORR_MAX_LEVELS];                        // tile / block rows (compact: image rows)
+    int64_t lsz[ECORR_MAX_LEVELS];                     // floats per query image
+};
+// T = the levels of g in the buffer at base; the entries past g.levels are cleared
+template <typename F>
+inline void level_table(const PyrGeom& g, F* base, LevelTable<F>* T) {
+    *T = LevelTable<F>{};
+    for (int i = 0; i < g.levels; ++i) {
+        T->lvl[i] = base + g.off[i];
+        T->lh[i] = g.h[i];
+        T->lw[i] = g.w[i];
+        T->lntx[i] = g.ntx[i];
+        T->lnty[i] = g.nty[i];
+        T->lsz[i] = g.sz[i];
+    }
+}
+
+struct BuildParams : LevelTable<float> {   // the table: the levels written (those the GEMM epilogue fuses: < fused_levels)
     const float* f1;
     const float* f2;
     int D, H, W;
@@ -47,10 +74,6 @@ struct BuildParams {
     int n_nt, n_ntx;    // n-tiles (target blocks); regular n-tiles per tile row
     int n_reg, band_y0;  // regular (8 x 16) n-tiles per m-tile; first row of the 4-row band tiles
     int fused_levels;   // levels written by the GEMM epilogue (<= 4)
-    float* lvl[4];
-    int lh[4], lw[4];
-    int lntx[4], lnty[4];   // tiles per tile row (0 = compact row-major) / tile rows of each fused level
-    int64_t lsz[4];         // floats per query image of each fused level
 };
 
 // stages (split build only; the fp32 build is one launch): 1 = operand pass, 2 = GEMM + fused
@@ -58,17 +81,13 @@ struct BuildParams {
 int launch_build(const BuildParams& P, int B, const PyrGeom& g, float* pyramid, hipStream_t stream, int stages = 3);
 int64_t build_split_workspace_bytes(int B, int D, int H, int W, int q_count);
 
-struct LookupParams {
+struct LookupParams : LevelTable<const float> {   // the table: the pyramid (read only)
     const float* coords;  // [B][2][q_count]
     float* out;           // [B][C][q_count]
     int H, W;
     int q_count;
     int levels, radius;
     int C;                // levels * (2r+1)^2
-    const float* lvl[ECORR_MAX_LEVELS];
-    int lh[ECORR_MAX_LEVELS], lw[ECORR_MAX_LEVELS];
-    int lntx[ECORR_MAX_LEVELS];      // tiles per tile row (0 = compact row-major)
-    int lsz[ECORR_MAX_LEVELS];       // floats per query image
     float* qmax;          // null, or [B][3 * levels][q_count]: per-query partial maxima of |out|
                           // (ecorr_lookup_qmax: the split convc1's column exponents)
     const int* scale;     // non-null: ecorr_lookup_presplit, out is the presplit layout and
@@ -78,17 +97,13 @@ struct LookupParams {
 int launch_lookup(const LookupParams& P, int B, hipStream_t stream);
 
 // grad.hip: the backward (ecorr_lookup_backward, ecorr_build_backward).  The gradient pyramid has the
-// pyramid's storage: lvl / lh / lw / lntx / lsz as in LookupParams.
-struct LookupGradParams {
+// pyramid's storage: the table is the gradient pyramid's.
+struct LookupGradParams : LevelTable<float> {
     const float* grad_out;   // [B][C][q_count]
     const float* coords;     // [B][2][q_count]
     int q_count;
     int levels, radius;
     int C;
-    float* lvl[ECORR_MAX_LEVELS];
-    int lh[ECORR_MAX_LEVELS], lw[ECORR_MAX_LEVELS];
-    int lntx[ECORR_MAX_LEVELS];
-    int64_t lsz[ECORR_MAX_LEVELS];
 };
 struct BuildGradParams {
     const float* T;          // the folded level 0 of the gradient pyramid: [B * q_count][sz], tiled

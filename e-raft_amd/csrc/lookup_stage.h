@@ -163,9 +163,9 @@ __device__ __forceinline__ void stage_issue(const WindowBuf<R, QB, PAIR>& st, co
     const int h = P.lh[lv], w = P.lw[lv], ntx = P.lntx[lv];
     const int64_t hw = P.lsz[lv];  // floats per query image
     const int64_t R0 = (int64_t)b * P.q_count + q0;   // first query row of the group
-    // interleaved levels (ntx < 0, ecorr_device.h): the slab starts at the 64-row group of R0
-    const int64_t g0 = R0 >> 6;
-    const float* __restrict__ lvbase = P.lvl[lv] + (ntx < 0 ? g0 * kGroup * hw : R0 * hw);
+    // this group's slab of the level (ecorr_device.h): from the 64-row group g0 of R0 when interleaved
+    const int64_t g0 = slab_g0(R0);
+    const float* __restrict__ lvbase = P.lvl[lv] + slab_first(ntx < 0, R0, hw);
 
     // ---- phase 1: stage windows, zeros outside the image (grid_sample padding_mode='zeros').
     // Work item = (query, window column or, PAIR, column pair from the even column xe at or left
@@ -179,16 +179,15 @@ __device__ __forceinline__ void stage_issue(const WindowBuf<R, QB, PAIR>& st, co
     using SR = StageRegs<R, QB, NTQ, PAIR>;
     constexpr int NPX = SR::NPX, ITEMS = SR::ITEMS, NCOL = SR::NCOL;
     const int nq = min(QB, P.q_count - q0);
-    const int64_t span = ntx < 0 ? (((R0 + nq - 1) >> 6) - g0 + 1) * kGroup * hw : nq * hw;
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lvbase), 0, (int)(span * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(lvbase), 0, (int)slab_bytes(ntx < 0, R0, nq, hw), 0x00020000);
     // row walk down a window column: in-block steps and block-row wraps (tiled: 4 x 8 tiles;
     // interleaved: bh x bw blocks; compact: every step is a wrap of one image row)
     const bool tiled = ntx > 0, ilv = ntx < 0;
     const int sy = ilv ? ilv_sy(lv) : 2, sx = ilv ? ilv_sx(lv) : 3;
     const int ymask = tiled || ilv ? (1 << sy) - 1 : 0;
     const int step_in = 4 << sx;
-    const int step_wrap = tiled ? 128 * ntx - 96 : ilv ? 4 * (-ntx * kGroup * (1 << (sy + sx)) - ymask * (1 << sx)) : 4 * w;
+    const int step_wrap = tiled ? 128 * ntx - 96 : ilv ? 4 * (-ntx * kGroup * ilv_bsz(lv) - ymask * (1 << sx)) : 4 * w;
     constexpr int OOB = 0x7ffffff0;   // beyond any slab: reads as 0
     auto& vals = sr.vals;
     auto& dst = sr.dst;
@@ -213,12 +212,9 @@ __device__ __forceinline__ void stage_issue(const WindowBuf<R, QB, PAIR>& st, co
         const int rlo = max(0, -y0), rhi = colin ? max(rlo, min(ny, h - y0)) : rlo;   // rhi >= rlo
         int off;
         if (tiled) {
-            off = (int)(gq * hw) * 4 + ((((y0 >> 2) * ntx + (x >> 3)) << 5) + ((y0 & 3) << 3) + (x & 7)) * 4;
+            off = (int)(gq * hw) * 4 + tiled_off(y0, x, ntx) * 4;
         } else if (ilv) {
-            const int64_t Rq = R0 + gq;
-            off = (int)((((Rq >> 6) - g0) * kGroup * hw +
-                         ((int64_t)((y0 >> sy) * -ntx + (x >> sx)) * kGroup + (Rq & (kGroup - 1))) * (1 << (sy + sx)) +
-                         ((y0 & ymask) << sx) + (x & ((1 << sx) - 1))) * 4);
+            off = (int)(ilv_pix_off(R0 + gq, g0, y0, x, lv, -ntx, hw) * 4);
         } else {
             off = (int)(gq * hw) * 4 + (y0 * w + x) * 4;
         }

@@ -145,6 +145,18 @@ def test_argument_validation_before_launch(ea):
     assert L.ecorr_build_split_gemm(1, 256, 8, 8, 65, 4, 8, 256, None) == _lib.ECORR_EINVAL
 
 
+def test_lookup_rejects_level0_image_past_31_bits(ea):
+    """The lookup kernels address inside a query image with 32-bit offsets, so a level-0 image of
+    more than 2^31 - 1 stored floats is refused before any launch: a 3 x 715827882 map (H*W = 2^31 - 2,
+    which the q_count check accepts) pads to 4 x 715827888 cells."""
+    L = ea.lib()
+    from eraft_amd import _lib
+    H, W = 3, 715827882
+    assert L.ecorr_lookup(8, 8, 1, H, W, 1, 1, 4, 8, None) == _lib.ECORR_EINVAL
+    assert L.ecorr_lookup_qmax(8, 8, 1, H, W, 1, 1, 4, 8, 8, None) == _lib.ECORR_EINVAL
+    assert L.ecorr_lookup(8, 8, 1, H, W, 1, 1, 33, 8, None) == _lib.ECORR_ERADIUS   # the radius is checked first
+
+
 def test_cpu_tensors_rejected_loudly(ea):
     import torch
     f = torch.zeros(1, 16, 8, 8)

@@ -724,7 +724,7 @@ def _st23(aux, levels):
     };""" % (aux, aux))]
     for lv in levels:
         rep += [("build.hip", f"if (FULL) fst2(r{lv}, v{lv},", f"if (FULL) fst2p(r{lv}, v{lv},"),
-                ("build.hip", f"else st2(r{lv}, (grp * G{lv}", f"else st2p(r{lv}, (grp * G{lv}")]
+                ("build.hip", f"else st2(r{lv}, (rowoff({lv}, rr)", f"else st2p(r{lv}, (rowoff({lv}, rr)")]
     return rep
 PATCHES["st23_plain"] = _st23(0, (2, 3))
 PATCHES["st3_plain"] = _st23(0, (3,))
