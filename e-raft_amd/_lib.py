@@ -88,6 +88,10 @@ SYMBOLS = {
     "ecorr_grid_sample_values": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p]),
     # (flow, mask, N, H, W, out, stream)
     "ecorr_upsample_flow": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    # its backward (added within ABI 17): (N, H, W, bytes*) /
+    # (grad_out, flow, mask, N, H, W, grad_flow, grad_mask, workspace, stream)
+    "ecorr_upsample_backward_workspace_size": (_i, [_i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_upsample_flow_backward": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     # (flow, B, h, w, out_u16, stream)
     "ecorr_flow_to_png16": (_i, [_p, _i, _i, _i, _p, _p]),
     # (in_u16, B, h, w, flow, valid, bad, stream)

@@ -416,11 +416,34 @@ ECORR_EXPORT int ecorr_grid_sample_values(const float* pts, int64_t n, int h, in
     return launch_splat(false, pts, 1, n, h, w, values, valid, workspace, (hipStream_t)stream);
 }
 
+namespace {
+
+// the upsampling kernels' limits: N rides a 16-bit grid axis, and 8 * H * W stays an int
+bool upsample_dims_ok(int N, int H, int W) {
+    return N > 0 && N <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= (1 << 26);
+}
+
+}  // namespace
+
 ECORR_EXPORT int ecorr_upsample_flow(const float* flow, const float* mask, int N, int H, int W, float* out,
                                      void* stream) {
-    if (!flow || !mask || !out || N <= 0 || N > 65535 || H <= 0 || W <= 0 || (int64_t)H * W > (1 << 26))
-        return ECORR_EINVAL;
+    if (!flow || !mask || !out || !upsample_dims_ok(N, H, W)) return ECORR_EINVAL;
     return launch_upsample_flow(flow, mask, N, H, W, out, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_upsample_backward_workspace_size(int N, int H, int W, int64_t* bytes) {
+    if (!bytes || !upsample_dims_ok(N, H, W)) return ECORR_EINVAL;
+    *bytes = upsample_backward_workspace_bytes(N, H, W);
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_upsample_flow_backward(const float* grad_out, const float* flow, const float* mask, int N,
+                                              int H, int W, float* grad_flow, float* grad_mask, void* workspace,
+                                              void* stream) {
+    if (!grad_out || !flow || !mask || (!grad_flow && !grad_mask) || !upsample_dims_ok(N, H, W)) return ECORR_EINVAL;
+    if (!workspace && upsample_backward_workspace_bytes(N, H, W) > 0) return ECORR_EINVAL;
+    return launch_upsample_flow_backward(grad_out, flow, mask, N, H, W, grad_flow, grad_mask, workspace,
+                                         (hipStream_t)stream);
 }
 
 ECORR_EXPORT int ecorr_flow_to_png16(const float* flow, int B, int h, int w, uint16_t* out, void* stream) {

@@ -177,6 +177,11 @@ int launch_rows_assemble(const float* chunks, int64_t chunk, int world, int B, i
                          hipStream_t stream);
 
 int launch_upsample_flow(const float* flow, const float* mask, int N, int H, int W, float* out, hipStream_t stream);
+// the backward: t = float[N][18][H*W] in the workspace, then the 9-tap gather into grad_flow; a null
+// grad_flow / grad_mask is not computed
+int64_t upsample_backward_workspace_bytes(int N, int H, int W);
+int launch_upsample_flow_backward(const float* grad_out, const float* flow, const float* mask, int N, int H, int W,
+                                  float* grad_flow, float* grad_mask, void* workspace, hipStream_t stream);
 int launch_png16_encode(const float* flow, int B, int h, int w, uint16_t* out, hipStream_t stream);
 int launch_png16_decode(const uint16_t* in, int B, int h, int w, float* flow, uint8_t* valid, int* bad,
                         hipStream_t stream);

@@ -6,8 +6,11 @@
     flow, valid = flow_16bit_to_float(png)   # utils/dsec_utils.py:66-83
 
 One HIP launch each (upsample.hip).  upsample_flow agrees with the reference within a few ulp
-(device expf); the codec is bit-exact.  No CPU path: inputs must be HIP tensors.
+(device expf) and is differentiable (two more launches in its backward); the codec is bit-exact.
+No CPU path: inputs must be HIP tensors.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -22,8 +25,51 @@ def _require_device(name, t, dtype):
         raise TypeError(f"{name} must be {dtype} (got {t.dtype})")
 
 
+def _upsample(flow, mask):
+    """The ecorr_upsample_flow launch on contiguous flow [N, 2, H, W] and mask (N * 576 * H * W elements)."""
+    N, _, H, W = flow.shape
+    with torch.cuda.device(flow.device):
+        out = torch.empty((N, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
+        _lib.check(_lib.lib().ecorr_upsample_flow(flow.data_ptr(), mask.data_ptr(), N, H, W, out.data_ptr(),
+                                                  _lib.stream_of(flow)), "upsample_flow")
+    return out
+
+
+class _UpsampleFn(torch.autograd.Function):
+    """upsample_flow with gradients for flow and mask (ecorr_upsample_flow_backward): the forward is
+    the plain launch; the backward recomputes the softmax from the saved inputs."""
+
+    @staticmethod
+    def forward(ctx, flow, mask):
+        ctx.save_for_backward(flow, mask)   # versioned: an in-place change before backward raises
+        return _upsample(flow.contiguous(), mask.contiguous())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        flow, mask = ctx.saved_tensors
+        N, _, H, W = flow.shape
+        go = grad_out.contiguous()   # ImagePadder.unpad: the gradient of a slice
+        fc, mc = flow.contiguous(), mask.contiguous()
+        need_flow, need_mask = ctx.needs_input_grad
+        with torch.cuda.device(fc.device):
+            nbytes = ctypes.c_int64()
+            _lib.check(_lib.lib().ecorr_upsample_backward_workspace_size(N, H, W, ctypes.byref(nbytes)),
+                       "upsample_flow backward")
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=fc.device)
+            g_flow = torch.empty((N, 2, H, W), dtype=torch.float32, device=fc.device) if need_flow else None
+            g_mask = torch.empty(mask.shape, dtype=torch.float32, device=fc.device) if need_mask else None
+            _lib.check(_lib.lib().ecorr_upsample_flow_backward(
+                go.data_ptr(), fc.data_ptr(), mc.data_ptr(), N, H, W,
+                None if g_flow is None else g_flow.data_ptr(), None if g_mask is None else g_mask.data_ptr(),
+                ws.data_ptr(), _lib.stream_of(fc)), "upsample_flow backward")
+        return g_flow, g_mask
+
+
 def upsample_flow(flow, mask):
-    """eraft.py:74-85: flow [N, 2, H, W], mask [N, 576, H, W] -> [N, 2, 8H, 8W]."""
+    """eraft.py:74-85: flow [N, 2, H, W], mask [N, 576, H, W] -> [N, 2, 8H, 8W].  Differentiable in
+    both inputs (ecorr_upsample_flow_backward; deterministic, first order only); with grad mode off, or
+    when neither input requires grad, it is the plain launch.  Either way the values are the same bits."""
     _require_device("flow", flow, torch.float32)
     _require_device("mask", mask, torch.float32)
     if flow.dim() != 4 or flow.shape[1] != 2:
@@ -31,12 +77,9 @@ def upsample_flow(flow, mask):
     N, _, H, W = flow.shape
     if mask.numel() != N * 576 * H * W:   # the reference's mask.view(N, 1, 9, 8, 8, H, W)
         raise RuntimeError(f"shape '[{N}, 1, 9, 8, 8, {H}, {W}]' is invalid for input of size {mask.numel()}")
-    flow, mask = flow.contiguous(), mask.contiguous()
-    with torch.cuda.device(flow.device):
-        out = torch.empty((N, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
-        _lib.check(_lib.lib().ecorr_upsample_flow(flow.data_ptr(), mask.data_ptr(), N, H, W, out.data_ptr(),
-                                                  _lib.stream_of(flow)), "upsample_flow")
-    return out
+    if torch.is_grad_enabled() and (flow.requires_grad or mask.requires_grad):
+        return _UpsampleFn.apply(flow, mask)
+    return _upsample(flow.contiguous(), mask.contiguous())
 
 
 def flow_to_png16(flow):

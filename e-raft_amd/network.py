@@ -185,9 +185,12 @@ class ERAFT(nn.Module):
     {'standard', 'warm_start'}; n_first_channels = voxel bins.  fuse_motion_corr=True replaces
     `corr_fn(coords1)` + BasicMotionEncoder's `relu(convc1(corr))` with the HIP lookup + convc1
     (CorrBlock.lookup_conv1x1_relu; its ECORR_CONVC1 mode); hip_upsample=True runs upsample_flow as
-    the one-pass HIP kernel (eraft_amd.upsample_flow).  differentiable_corr=True
+    the one-pass HIP kernel (eraft_amd.upsample_flow), which is differentiable in
+    flow and mask (its HIP backward), so a loss on the predictions trains through
+    it.  differentiable_corr=True
     builds the CorrBlock with differentiable=True, so a loss on the predictions trains fnet (not with
-    fuse_motion_corr).  The defaults keep the reference's call pattern exactly."""
+    fuse_motion_corr).  With both, the native ops run on both ends of the GRU loop in training.  The
+    defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
     corr_radius = 4

@@ -258,6 +258,22 @@ int ecorr_grid_sample_values(const float* pts, int64_t n, int h, int w, float* v
  * Replaces: model/eraft.py:74-85. */
 int ecorr_upsample_flow(const float* flow, const float* mask, int N, int H, int W, float* out, void* stream);
 
+/* The backward of ecorr_upsample_flow (two entries added within ABI 17: purely additive, the version
+ * is unchanged).  grad_out float[N][2][8H][8W] contiguous, flow and mask the forward's inputs ->
+ * grad_flow float[N][2][H][W] and grad_mask float[N][576][H][W].  Either of the two may be NULL and is
+ * then not computed; both NULL is ECORR_EINVAL.  Every element of a non-null output is overwritten
+ * (never accumulated into), and nothing else is written but the workspace.  The softmax is recomputed
+ * from mask by the forward's definition (nothing mask-sized is saved).  Deterministic: no float
+ * atomics, one writer per output cell and a fixed summation order (j, then i, then k ascending), so
+ * equal inputs give bitwise equal gradients.  workspace: ecorr_upsample_backward_workspace_size bytes
+ * of device memory (float[N][18][H*W], contents undefined before and after), required whichever
+ * gradients are asked for; NULL is ECORR_EINVAL.  N, H, W as ecorr_upsample_flow (N <= 65535,
+ * H * W <= 2^26, any H, W >= 1); validation happens before any launch.
+ * Replaces: autograd of eraft.py:74-85. */
+int ecorr_upsample_backward_workspace_size(int N, int H, int W, int64_t* bytes);
+int ecorr_upsample_flow_backward(const float* grad_out, const float* flow, const float* mask, int N, int H, int W,
+                                 float* grad_flow, float* grad_mask, void* workspace, void* stream);
+
 /* DSEC submission encoding: flow float[B][2][h][w] -> out uint16[B][h][w][3] =
  * (u16)rint(flow * 128 + 2^15) with numpy's x86 float32 -> uint16 cast, channel 2 = 0.
  * Bit-exact.  Replaces: utils/visualization.py:81-84 (before imageio.imwrite). */

@@ -702,6 +702,46 @@ PATCHES["up_stplain"] = [("upsample.hip", """        __builtin_nontemporal_store
         __builtin_nontemporal_store(floatx4{res[c][4], res[c][5], res[c][6], res[c][7]}, (floatx4*)(o + 4));""",
                           """        *(floatx4*)o = floatx4{res[c][0], res[c][1], res[c][2], res[c][3]};
         *(floatx4*)(o + 4) = floatx4{res[c][4], res[c][5], res[c][6], res[c][7]};""")]
+# upsampling backward, the reduction of t over the 8 sub-rows: option A of DESIGN §3.5 -- sub-row i on
+# blockIdx.z of 256-thread workgroups (the forward's shape), each thread's partial t to a workspace
+# 8x the size ([N][8][18][HW]), the gather kernel sums the 8 partials of every tap with i ascending
+# (the same summation order, so the same bits).  The tree reduces through LDS in a 512-thread workgroup.
+PATCHES["upbw_partials"] = [
+    ("upsample.hip", "constexpr int UBP = 64; ", "constexpr int UBP = 256;"),
+    ("upsample.hip", "constexpr int NTB = 8 * UBP;", "constexpr int NTB = UBP;    "),
+    ("upsample.hip", "    __shared__ float red[FLOW ? 8 * 18 * UBP : 1];\n", ""),
+    ("upsample.hip", "    const int lane = threadIdx.x & (UBP - 1), i = threadIdx.x / UBP;",
+     "    const int lane = threadIdx.x, i = blockIdx.z;"),
+    ("upsample.hip", """            for (int k = 0; k < 9; ++k) red[(i * 18 + c * 9 + k) * UBP + lane] = tt[c][k];
+        __syncthreads();
+        for (int e = threadIdx.x; e < 18 * UBP; e += NTB) {
+            const int ck = e / UBP, l = e & (UBP - 1);
+            float acc = red[ck * UBP + l];
+#pragma unroll
+            for (int ii = 1; ii < 8; ++ii) acc = __fadd_rn(acc, red[(ii * 18 + ck) * UBP + l]);
+            if (p0 + l < HW) t[((int64_t)n * 18 + ck) * HW + p0 + l] = acc;
+        }
+""", """            for (int k = 0; k < 9; ++k)
+                if (p < HW) t[(((int64_t)n * 8 + i) * 18 + c * 9 + k) * HW + p] = tt[c][k];
+"""),
+    ("upsample.hip", """    const float* tc = t + ((int64_t)n * 18 + c * 9) * HW;""",
+     """    const float* tc = t + ((int64_t)n * 8 * 18 + c * 9) * HW;"""),
+    ("upsample.hip", """            acc = __fadd_rn(acc, tc[(int64_t)k * HW + sy * W + sx]);""",
+     """        {
+            const float* tk = tc + (int64_t)k * HW + sy * W + sx;
+            float part = tk[0];
+#pragma unroll
+            for (int ii = 1; ii < 8; ++ii) part = __fadd_rn(part, tk[(int64_t)ii * 18 * HW]);
+            acc = __fadd_rn(acc, part);
+        }"""),
+    ("upsample.hip", "return (int64_t)N * 18 * H * W * sizeof(float);", "return (int64_t)N * 8 * 18 * H * W * sizeof(float);"),
+    ("upsample.hip", "const dim3 grid((unsigned)((HW + UBP - 1) / UBP), (unsigned)N);",
+     "const dim3 grid((unsigned)((HW + UBP - 1) / UBP), (unsigned)N, 8);")]
+# upsampling backward: the 72 grad_mask stores with the default policy (the tree: non-temporal, as the
+# forward's output stores; 83.6 vs 69.1 us at DSEC B = 16, profiles/upsample_backward/ab_variants.txt)
+PATCHES["upbw_stplain"] = [("upsample.hip", """                    __builtin_nontemporal_store(__fmul_rn(m[k], __fsub_rn(a[k], dot)),
+                                                &grad_mask[row + ((int64_t)k * 64 + j) * HW]);""",
+                            """                    grad_mask[row + ((int64_t)k * 64 + j) * HW] = __fmul_rn(m[k], __fsub_rn(a[k], dot));""")]
 # lookup: window loads non-temporal (aux 2) -- the upsampling's lesson checked the other way
 PATCHES["lk_ldnt"] = [("lookup_stage.h", "const uint2v u = __builtin_amdgcn_raw_buffer_load_b64(rsrc, need ? off : OOB, 0, 0);",
                        "const uint2v u = __builtin_amdgcn_raw_buffer_load_b64(rsrc, need ? off : OOB, 0, 2);"),
