@@ -62,6 +62,10 @@ SYMBOLS = {
     "ecorr_conv1x1_split_size": (_i, [_i, _i, ctypes.POINTER(_i64)]),
     "ecorr_conv1x1_split_pack": (_i, [_p, _i, _i, _p, _p]),
     "ecorr_conv1x1_relu_split": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p]),
+    # its backward (added within ABI 17): (B, C, Q, O, bytes*) /
+    # (grad_out, out, in, packed_t, B, C, Q, O, grad_in, grad_weight, grad_bias, workspace, stream)
+    "ecorr_conv1x1_relu_backward_workspace_size": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_conv1x1_relu_backward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     # as ecorr_lookup + qmax[B][3*levels][q_count] (before stream)
     "ecorr_lookup_qmax": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # presplit convc1 (ABI 16): (fmap1, fmap2, B, D, H, W, scale[B*H*W + B], stream)
@@ -266,7 +270,8 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
 
 # Packed convc1 weights.  kind "fused": ecorr_conv1x1_pack (the fused lookup + convc1 kernel's fp32
 # MFMA fragment order); "split": ecorr_conv1x1_split_pack (hi/lo f16 fragments + row exponents for
-# ecorr_conv1x1_relu_split).  ERAFT.forward builds one CorrBlock per forward and calls convc1 `iters`
+# ecorr_conv1x1_relu_split); "split_t": the same pack of the transposed weight (the backward's
+# grad_in, ecorr_conv1x1_relu_backward).  ERAFT.forward builds one CorrBlock per forward and calls convc1 `iters`
 # times with the same weight, so the caller passes a cache it owns (the CorrBlock instance's): the
 # weight is re-laid once per block.  The key holds the tensor identity, its storage pointer and its
 # version counter; a change through .data that keeps all three (w.data.mul_(...)) between two calls
@@ -280,7 +285,13 @@ def packed_conv1x1_weight(weight, O, C, kind, st, cache):
         return ent[2]
     wt = weight.reshape(O, C).contiguous()
     n = ctypes.c_int64()
-    if kind in ("split", "presplit"):
+    if kind == "split_t":   # the transposed weight [C][O] in the split pack: grad_in of the backward
+        wt = wt.t().contiguous()
+        check(lib().ecorr_conv1x1_split_size(C, O, ctypes.byref(n)), "convc1 transposed weight pack")
+        packed = torch.empty(n.value, dtype=torch.uint8, device=weight.device)
+        check(lib().ecorr_conv1x1_split_pack(wt.data_ptr(), C, O, packed.data_ptr(), st),
+              "convc1 transposed weight pack")
+    elif kind in ("split", "presplit"):
         if kind == "split":
             check(lib().ecorr_conv1x1_split_size(O, C, ctypes.byref(n)), "convc1 split weight pack")
         else:
@@ -382,3 +393,31 @@ def lookup_conv1x1_relu(pyramid, coords, shape, q_count, levels, radius, weight,
                 pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, wt.data_ptr(), bptr, O,
                 out.data_ptr(), st), f"{what} lookup+conv1x1+relu")
     return out
+
+
+def conv1x1_relu_backward(grad_out, out, corr, weight, cache, want_in, want_weight, want_bias, what):
+    """ecorr_conv1x1_relu_backward for out = relu(conv1x1(corr, weight, bias)): (grad_in, grad_weight,
+    grad_bias) on grad_out's current stream, None where not wanted.  grad_out, out: contiguous
+    [B, O, ...]; corr: the conv's contiguous input [B, C, ...] (needed for want_weight only, else
+    None); cache: the block's packed-weight cache (the transposed pack, kind "split_t", once per
+    block, on this stream).  The workspace is a temporary from the caching allocator."""
+    B, O = out.shape[0], out.shape[1]
+    C = weight.numel() // O
+    Q = out.numel() // (B * O)
+    dev = out.device
+    with on_device(dev):
+        st = stream_of(out)
+        nbytes = _i64()
+        check(lib().ecorr_conv1x1_relu_backward_workspace_size(B, C, Q, O, ctypes.byref(nbytes)), what)
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        pk = packed_conv1x1_weight(weight, O, C, "split_t", st, cache) if want_in else None
+        gi = torch.empty((B, C) + tuple(out.shape[2:]), dtype=torch.float32, device=dev) if want_in else None
+        gw = torch.empty(weight.shape, dtype=torch.float32, device=dev) if want_weight else None
+        gb = torch.empty(O, dtype=torch.float32, device=dev) if want_bias else None
+
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+        check(lib().ecorr_conv1x1_relu_backward(
+            grad_out.data_ptr(), out.data_ptr(), ptr(corr) if want_weight else None, ptr(pk), B, C, Q, O,
+            ptr(gi), ptr(gw), ptr(gb), ws.data_ptr(), st), what)
+    return gi, gw, gb

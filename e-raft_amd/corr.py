@@ -28,8 +28,19 @@ then runs once, after all of them, turns the gradient pyramid into the two fmap 
 frees it.  Deterministic (no atomics).  Contract of the differentiable block: coords are detached
 (coords.requires_grad raises; eraft.py:127 detaches them; there is no coordinate gradient), every
 pyramid level is at least 2 x 2 (the reference's samples of a 1-pixel axis are NaN), D >= 1, one
-backward per block (a second one raises), single GPU; lookup_conv1x1_relu, bilinear_sampler and
-RowShardedCorrBlock stay forward-only.
+backward per block (a second one raises), single GPU; bilinear_sampler and RowShardedCorrBlock stay
+forward-only.
+
+Training through convc1 (the same opt-in): on a differentiable block,
+`corr_fn.lookup_conv1x1_relu(coords, weight, bias)` is a Function of (handle, coords, weight, bias)
+whenever grad mode is on and the block is live or weight / bias require grad.  Its forward is the
+plain call's launch sequence in the requested mode (bitwise the same values) and saves only coords,
+weight, bias and its own output; the backward (ecorr_conv1x1_relu_backward, csrc/conv_grad.hip;
+DESIGN.md §3.3.1) masks the incoming gradient with the saved output, recomputes the lookup for the
+weight gradient instead of keeping it alive (99.5 MB per iteration at DSEC B = 16), runs grad_corr on
+the f16 matrix cores (the split conv with the transposed weight, packed once per block) and feeds it
+to ecorr_lookup_backward when the block is live.  With frozen fmaps only weight and bias receive
+gradients and no gradient pyramid is allocated.  Deterministic (no atomics).
 
 Numerics: the default build sums each product as f16 lo*hi + hi*lo + hi*hi of per-pixel-scaled
 operands: within 1e-5 normwise of the reference and closer to fp64 than its fp32
@@ -128,13 +139,70 @@ class _LookupFn(torch.autograd.Function):
             return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None
 
 
+class _LookupConvFn(torch.autograd.Function):
+    """(handle, coords, weight, bias) -> relu(conv1x1(lookup(coords))).  handle is None when the block
+    is not live (frozen fmaps): then only weight and bias get gradients.  corr is not saved: the
+    backward recomputes it (ecorr_lookup) when the weight needs its gradient."""
+
+    @staticmethod
+    def forward(ctx, handle, coords, weight, bias, blk, mode):
+        B, _, H, W = blk._shape
+        out = _lib.lookup_conv1x1_relu(
+            blk._pyramid, coords.contiguous(), (B, H, W), H * W, blk.num_levels, blk.radius, weight, bias, mode,
+            lambda O: torch.empty((B, O, H, W), dtype=torch.float32, device=blk._device), blk._wcache, "CorrBlock",
+            column_scale=blk._column_scale)
+        # what the backward reads of the block, not the block: the pyramid, the geometry, the shared
+        # gradient state (None: not live) and the packed-weight cache
+        ctx.pyramid, ctx.state, ctx.wcache = blk._pyramid, blk._grad, blk._wcache
+        ctx.geom = (blk._shape, blk.num_levels, blk.radius)
+        ctx.save_for_backward(coords, out, weight, bias)   # versioned: an in-place change raises in backward
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        st = ctx.state
+        if st is not None and st.consumed:
+            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
+                               "consumed (one backward per differentiable block)")
+        coords, out, weight, bias = ctx.saved_tensors
+        (B, _, H, W), levels, radius = ctx.geom
+        want_in = st is not None and ctx.needs_input_grad[0]
+        want_w = ctx.needs_input_grad[2]
+        want_b = bias is not None and ctx.needs_input_grad[3]
+        dev = out.device
+        go = grad_out.contiguous()
+        cc = coords.contiguous()
+        with _lib.on_device(dev):
+            handle_grad = None if st is None else torch.zeros(1, dtype=torch.float32, device=dev)
+            if not (want_in or want_w or want_b):
+                return handle_grad, None, None, None, None, None
+            corr = None
+            if want_w:   # the conv's input again (44 us at DSEC B = 16) instead of 99.5 MB saved per call
+                K = 2 * radius + 1
+                corr = torch.empty((B, levels * K * K, H, W), dtype=torch.float32, device=dev)
+                _lib.lookup(ctx.pyramid, cc, (B, H, W), H * W, levels, radius, corr, "CorrBlock")
+            gi, gw, gb = _lib.conv1x1_relu_backward(go, out, corr, weight, ctx.wcache, want_in, want_w, want_b,
+                                                    "CorrBlock lookup+conv1x1+relu backward")
+            del corr
+            if want_in:
+                if st.G is None:
+                    st.G = torch.zeros(st.numel, dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib().ecorr_lookup_backward(
+                    gi.data_ptr(), cc.data_ptr(), B, H, W, H * W, levels, radius, st.G.data_ptr(),
+                    _lib.stream_of(go)), "CorrBlock lookup backward")
+        return handle_grad, None, gw, gb, None, None
+
+
 class CorrBlock:
     """All-pairs correlation pyramid + radius-r lookup (reference: model/corr.py:12-60).
-    differentiable=True (keyword only): gradients for fmap1 / fmap2 (module docstring)."""
+    differentiable=True (keyword only): gradients for fmap1 / fmap2, and through
+    lookup_conv1x1_relu for its weight and bias too (module docstring)."""
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, differentiable=False):
         self.num_levels = num_levels
         self.radius = radius
+        self._differentiable = bool(differentiable)   # lookup_conv1x1_relu: weight / bias gradients without live fmaps
         _require_device_f32("fmap1", fmap1)
         _require_device_f32("fmap2", fmap2)
         # the gradient path is live only when asked for and needed; otherwise: the plain block
@@ -231,18 +299,30 @@ class CorrBlock:
                    falls back to "split" when the fmaps are gone or changed in place since the build;
                    measured no faster than "split" (DESIGN.md §3.3);
           "fused"  ecorr_lookup_conv1x1_relu_packed: one kernel, the lookup tile never leaves the
-                   CU, an exact c-ordered fp32 MFMA sum (radius 4, num_levels <= 4, O a multiple of 64)."""
+                   CU, an exact c-ordered fp32 MFMA sum (radius 4, num_levels <= 4, O a multiple of 64).
+        A block built with differentiable=True trains through this call (grad mode on, and the block
+        live or weight / bias requiring grad): the same launches in the forward (bitwise the plain
+        block's values), and in the backward ecorr_conv1x1_relu_backward on the recomputed lookup, then
+        ecorr_lookup_backward into the block's gradient pyramid when the block is live (module
+        docstring).  coords that require grad raise, as in corr_fn(coords)."""
         mode = _lib.convc1_mode(mode, presplit=True)
-        if self._grad is not None:
-            raise RuntimeError("eraft_amd CorrBlock.lookup_conv1x1_relu is forward-only: a differentiable block "
-                               "gives gradients through corr_fn(coords) only")
         B, _, H, W = self._shape
         _require_device_f32("coords", coords)
-        _no_grad_inputs(coords)
+        train = self._differentiable and torch.is_grad_enabled() and (
+            self._grad is not None or (isinstance(weight, torch.Tensor) and weight.requires_grad)
+            or (isinstance(bias, torch.Tensor) and bias.requires_grad))
+        if train and coords.requires_grad:
+            raise RuntimeError("differentiable CorrBlock: coords requires grad; detach it (as eraft.py:127 does), "
+                               "there is no gradient with respect to the coordinates")
+        if not train:
+            _no_grad_inputs(coords)
         if tuple(coords.shape) != (B, 2, H, W):
             raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
         if coords.device != self._device:
             raise RuntimeError("coords is on a different device than the pyramid")
+        if train:
+            _require_device_f32("weight", weight)
+            return _LookupConvFn.apply(self._handle, coords, weight, bias, self, mode)
         return _lib.lookup_conv1x1_relu(
             self._pyramid, coords.contiguous(), (B, H, W), H * W, self.num_levels, self.radius, weight, bias, mode,
             lambda O: torch.empty((B, O, H, W), dtype=torch.float32, device=self._device), self._wcache, "CorrBlock",

@@ -319,6 +319,21 @@ ECORR_EXPORT int ecorr_conv1x1_relu_split(const float* in, int B, int C, int Q, 
     return launch_conv1x1_relu_split(in, B, C, Q, qmax, G, packed, bias, O, out, (hipStream_t)stream);
 }
 
+ECORR_EXPORT int ecorr_conv1x1_relu_backward_workspace_size(int B, int C, int Q, int O, int64_t* bytes) {
+    if (!bytes) return ECORR_EINVAL;
+    return conv1x1_relu_backward_workspace_bytes(B, C, Q, O, bytes);
+}
+
+ECORR_EXPORT int ecorr_conv1x1_relu_backward(const float* grad_out, const float* out, const float* in,
+                                             const void* packed_t, int B, int C, int Q, int O, float* grad_in,
+                                             float* grad_weight, float* grad_bias, void* workspace, void* stream) {
+    if (!grad_out || !out || !workspace || (!grad_in && !grad_weight && !grad_bias)) return ECORR_EINVAL;
+    if ((grad_in && !packed_t) || (grad_weight && !in)) return ECORR_EINVAL;
+    if (grad_in && (grad_in == grad_out || grad_in == out || grad_in == in)) return ECORR_EINVAL;
+    return launch_conv1x1_relu_backward(grad_out, out, in, packed_t, B, C, Q, O, grad_in, grad_weight, grad_bias,
+                                        workspace, (hipStream_t)stream);
+}
+
 ECORR_EXPORT int ecorr_split_column_scale(const float* fmap1, const float* fmap2, int B, int D, int H, int W,
                                           int* scale, void* stream) {
     if (!fmap1 || !fmap2 || !scale) return ECORR_EINVAL;

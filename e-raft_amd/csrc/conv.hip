@@ -91,13 +91,21 @@ __global__ __launch_bounds__(SNT) void split_pack_kernel(const float* __restrict
 // PRE: `in` is the presplit corr (ecorr_lookup_presplit): the B fragment of chunk c is two 16-byte
 // loads (hi, lo of group 2 c + kh) instead of 8 dword loads and the split, and the query exponent
 // comes from `scale` (qmax unused); the weight columns are packed in the presplit order.
-template <int PD, bool PRE = false>
+// The RELU flag rides in PDF = PD | kNoRelu: without it the epilogue skips the ReLU and nothing
+// else changes (grad_in of the backward, conv_grad.hip: the same product with the transposed
+// weight).  It is no third template parameter because that would rename the two forward kernels,
+// whose mangled names tests/test_isa_waits.py looks up; with the flag clear they compile to the
+// instructions they had before (profiles/motion_backward/isa_identity.txt).
+constexpr int kNoRelu = 0x100;
+template <int PDF, bool PRE = false>
 __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restrict__ in, int C, int Q,
                                                             const float* __restrict__ qmax, int G,
                                                             const char* __restrict__ packed,
                                                             const float* __restrict__ bias, int O,
                                                             float* __restrict__ out,
                                                             const int* __restrict__ scale) {
+    constexpr int PD = PDF & 0xff;
+    constexpr bool RELU = !(PDF & kNoRelu);
     constexpr int NB = 3;
     // ALL LDS in one object: with a second __shared__ object hipcc waits vmcnt(0) before every
     // ds_read while an LDS-DMA is in flight (cdna_hip_programming.md, the second-__shared__ trap)
@@ -314,7 +322,7 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
             for (int t = 0; t < 4; ++t) {
                 float v = ldexpf(acc[i][4 * g + t], -(eo[t] + eq));
                 v = v + bo[t];   // a missing bias is 0 (v + 0 = v for every v but -0, which ReLU maps to 0)
-                v = v < 0.f ? 0.f : v;   // torch.relu: NaN stays NaN
+                if constexpr (RELU) v = v < 0.f ? 0.f : v;   // torch.relu: NaN stays NaN
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), osrc, obase + (ob * SO + ol + t) * qs, 0,
                                                       2);   // nt: 52.2 vs 53.9 us (r4l_ab_conv.txt)
             }
@@ -322,6 +330,16 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
 }
 
 constexpr int kConvPD = 2;   // query-column prefetch distance (chunks)
+
+// the split kernels' limits for in float[B][C][Q] -> out float[B][O][Q] with G partial maxima (0: none)
+bool split_geometry_ok(int B, int C, int Q, int O, int G) {
+    if (G && (G < 0 || (int64_t)G * Q * 4 >= 0x7fffffffLL)) return false;
+    if (B <= 0 || C <= 0 || Q <= 0 || O <= 0 || B > 65535 || split_oblocks(O) > 65535) return false;
+    // 32-bit buffer offsets: a lane past Q reads from C*Q on, the prefetch reaches 3 chunks past C; the stores
+    // likewise from O*Q up to the output block's last row
+    return (int64_t)(2 * C + 4 * SKC) * Q * 4 < 0x7fffffffLL &&
+           (int64_t)(O + split_oblocks(O) * SO) * Q * 4 < 0x7fffffffLL;
+}
 
 }  // namespace
 
@@ -341,17 +359,24 @@ int launch_conv1x1_split_pack(const float* wt, int O, int C, void* packed, hipSt
 
 int launch_conv1x1_relu_split(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
                               const float* bias, int O, float* out, hipStream_t stream) {
-    if (qmax && (G <= 0 || (int64_t)G * Q * 4 >= 0x7fffffffLL)) return ECORR_EINVAL;
-    if (B <= 0 || C <= 0 || Q <= 0 || O <= 0 || B > 65535 || split_oblocks(O) > 65535) return ECORR_EINVAL;
-    // 32-bit buffer offsets: a lane past Q reads from C*Q on, the prefetch reaches 3 chunks past C; the stores
-    // likewise from O*Q up to the output block's last row
-    if ((int64_t)(2 * C + 4 * SKC) * Q * 4 >= 0x7fffffffLL ||
-        (int64_t)(O + split_oblocks(O) * SO) * Q * 4 >= 0x7fffffffLL)
-        return ECORR_EINVAL;
+    if (qmax && G <= 0) return ECORR_EINVAL;
+    if (!split_geometry_ok(B, C, Q, O, qmax ? G : 0)) return ECORR_EINVAL;
     if ((const void*)in == (const void*)out) return ECORR_EINVAL;
     const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
     hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax, G,
                        (const char*)packed, bias, O, out, nullptr);
+    return hip_status();
+}
+
+bool conv1x1_split_geometry_ok(int B, int C, int Q, int O, int G) { return split_geometry_ok(B, C, Q, O, G); }
+
+int launch_conv1x1_split_linear(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
+                                int O, float* out, hipStream_t stream) {
+    if (!qmax || G <= 0 || !split_geometry_ok(B, C, Q, O, G)) return ECORR_EINVAL;
+    if ((const void*)in == (const void*)out) return ECORR_EINVAL;
+    const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
+    hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD | kNoRelu, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax,
+                       G, (const char*)packed, nullptr, O, out, nullptr);
     return hip_status();
 }
 

@@ -130,6 +130,18 @@ int launch_conv1x1_split_pack(const float* wt, int O, int C, void* packed, hipSt
 int64_t conv1x1_presplit_bytes(int O, int levels);
 int launch_conv1x1_relu_split(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
                               const float* bias, int O, float* out, hipStream_t stream);
+// the same product without bias and ReLU, qmax required (grad_in of the backward: in = the masked
+// gradient, packed = the transposed weight's pack); and whether a geometry is within both kernels'
+// limits (G partial maxima, 0 = none)
+int launch_conv1x1_split_linear(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
+                                int O, float* out, hipStream_t stream);
+bool conv1x1_split_geometry_ok(int B, int C, int Q, int O, int G);
+// conv_grad.hip: the backward of relu(conv1x1) (ecorr_conv1x1_relu_backward); a null grad_in /
+// grad_weight / grad_bias is not computed.  The size query returns the geometry's status.
+int conv1x1_relu_backward_workspace_bytes(int B, int C, int Q, int O, int64_t* bytes);
+int launch_conv1x1_relu_backward(const float* grad_out, const float* out, const float* in, const void* packed_t, int B,
+                                 int C, int Q, int O, float* grad_in, float* grad_weight, float* grad_bias,
+                                 void* workspace, hipStream_t stream);
 
 // Presplit corr (ecorr_lookup_presplit -> ecorr_conv1x1_relu_presplit), radius 4, L <= 4 levels,
 // C = 81 L channels at K = 88 L positions.  Channel ch = 81 lv + 27 part + k (lookup_cols_reg: wave

@@ -189,18 +189,24 @@ class ERAFT(nn.Module):
     flow and mask (its HIP backward), so a loss on the predictions trains through
     it.  differentiable_corr=True
     builds the CorrBlock with differentiable=True, so a loss on the predictions trains fnet (not with
-    fuse_motion_corr).  With both, the native ops run on both ends of the GRU loop in training.  The
-    defaults keep the reference's call pattern exactly."""
+    fuse_motion_corr).  With both, the native ops run on both ends of the GRU loop in training.
+    train_motion_corr=True is fuse_motion_corr on a differentiable CorrBlock: every iteration runs
+    CorrBlock.lookup_conv1x1_relu in the forward and its HIP backward, so fnet and
+    convc1 train through it; under torch.no_grad() its predictions are bitwise fuse_motion_corr's.
+    The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
     corr_radius = 4
 
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
-                 differentiable_corr=False):
+                 differentiable_corr=False, train_motion_corr=False):
         super().__init__()
-        if differentiable_corr and fuse_motion_corr:
+        if train_motion_corr:
+            differentiable_corr = fuse_motion_corr = True
+        elif differentiable_corr and fuse_motion_corr:
             raise ValueError("differentiable_corr=True cannot be combined with fuse_motion_corr=True: the fused "
                              "lookup + convc1 is forward-only")
+        self.train_motion_corr = train_motion_corr
         self.differentiable_corr = differentiable_corr
         self.fuse_motion_corr = fuse_motion_corr
         self.hip_upsample = hip_upsample

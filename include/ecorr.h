@@ -179,6 +179,35 @@ int ecorr_conv1x1_split_pack(const float* weight, int O, int C, void* packed, vo
 int ecorr_conv1x1_relu_split(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
                              const float* bias, int O, float* out, void* stream);
 
+/* The backward of ecorr_conv1x1_relu_split's function (added within ABI 17), for any in float[B][C][Q]:
+ * with grad_out, out float[B][O][Q] (out: the forward's post-ReLU result) and the masked gradient
+ *   gm[b][o][p] = out[b][o][p] <= 0 ? 0 : grad_out[b][o][p]     (ATen threshold_backward: a NaN in
+ *                                                                 out passes the gradient through)
+ *   grad_in     float[B][C][Q] = sum_o W[o][c] * gm[b][o][p]
+ *   grad_weight float[O][C]    = sum_{b,p} gm[b][o][p] * in[b][c][p]
+ *   grad_bias   float[O]       = sum_{b,p} gm[b][o][p]
+ * Each output may be NULL and is then not computed (all three NULL: ECORR_EINVAL); every element of
+ * a non-null output is overwritten, never accumulated into; nothing else is written but the
+ * workspace (ecorr_conv1x1_relu_backward_workspace_size bytes, required; contents undefined before
+ * and after).  packed_t: what ecorr_conv1x1_split_pack writes for the TRANSPOSED weight float[C][O],
+ * called as (wT, C, O) (size: ecorr_conv1x1_split_size(C, O)); needed only for grad_in.  in: needed
+ * only for grad_weight.  grad_in must not be grad_out, out or in.
+ * grad_in runs on the f16 matrix cores with split operands like the forward: normwise within 1e-5
+ * of fp64, and a non-finite gm value makes that query's whole grad_in column NaN.  grad_weight sums
+ * fp32 products on v_mfma_f32_32x32x2_f32 in slabs of at most 1024 queries of one batch item, the
+ * slab partials added in ascending order; grad_bias likewise from per-block partial sums.
+ * Deterministic: no atomics, one writer per cell, summation orders fixed by the shape; equal inputs
+ * give bitwise equal gradients.
+ * ECORR_EINVAL before any launch: a NULL required pointer, B outside [1, 65535], C, Q or O < 1, or
+ * the 32-bit offset limits of ecorr_conv1x1_relu_split with the roles of C and O swapped; the size
+ * query returns the same status for the same geometry.
+ * Replaces: autograd of update.py:67,74. */
+int ecorr_conv1x1_relu_backward_workspace_size(int B, int C, int Q, int O, int64_t* bytes);
+int ecorr_conv1x1_relu_backward(const float* grad_out, const float* out, const float* in, const void* packed_t,
+                                int B, int C, int Q, int O,
+                                float* grad_in, float* grad_weight, float* grad_bias,
+                                void* workspace, void* stream);
+
 /* Presplit convc1 (ABI 16): the lookup writes corr already split for the split conv, so the conv
  * loads each 8-channel B fragment as two 16-byte pieces and runs no split arithmetic and no maxima.
  * The query's scale must be known before any level's samples are written, so it is a bound, not
