@@ -23,6 +23,12 @@ ECORR_ESHAPE = -2
 ECORR_ERADIUS = -3
 ECORR_ELEVELS = -4
 
+# ecorr_lookup_as's out_format (include/ecorr.h) per output dtype
+ECORR_OUT_F32 = 0
+ECORR_OUT_F16 = 1
+ECORR_OUT_BF16 = 2
+OUT_FORMATS = {torch.float32: ECORR_OUT_F32, torch.float16: ECORR_OUT_F16, torch.bfloat16: ECORR_OUT_BF16}
+
 _lib = None
 
 _i = ctypes.c_int
@@ -47,6 +53,9 @@ SYMBOLS = {
     "ecorr_build_split_gemm": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (pyramid, coords, B, H, W, q_count, levels, radius, out, stream)
     "ecorr_lookup": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    # a 16-bit (or fp32) output element (added within ABI 17):
+    # (pyramid, coords, B, H, W, q_count, levels, radius, out_format, out, stream)
+    "ecorr_lookup_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     # the backward (ABI 17): (grad_out, coords, B, H, W, q_count, levels, radius, grad_pyramid, stream)
     "ecorr_lookup_backward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     # (grad_pyramid, fmap1, fmap2, B, D, H, W, q_count, levels, grad_fmap1, grad_fmap2, stream)
@@ -314,12 +323,26 @@ def packed_conv1x1_weight(weight, O, C, kind, st, cache):
 def lookup(pyramid, coords, shape, q_count, levels, radius, out, what):
     """The ecorr_lookup launch of every block: the q_count queries of contiguous coords
     [B][2][q_count] into out ([B][C][q_count] fp32, returned), on the current stream of the pyramid's
-    device.  shape = (B, H, W) of the build; what: the class name for error texts."""
+    device.  shape = (B, H, W) of the build; what: the class name for error texts.  A float16 /
+    bfloat16 out takes ecorr_lookup_as: the same launch with the 16-bit store."""
     B, H, W = shape
     with on_device(pyramid.device):
-        check(lib().ecorr_lookup(pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius,
-                                 out.data_ptr(), stream_of(out)), f"{what} lookup")
+        if out.dtype == torch.float32:
+            check(lib().ecorr_lookup(pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius,
+                                     out.data_ptr(), stream_of(out)), f"{what} lookup")
+        else:
+            check(lib().ecorr_lookup_as(pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius,
+                                        OUT_FORMATS[out.dtype], out.data_ptr(), stream_of(out)), f"{what} lookup")
     return out
+
+
+def lookup_out_dtype(out_dtype):
+    """The dtype of a lookup output for the out_dtype argument of CorrBlock.__call__: None = float32."""
+    if out_dtype is None:
+        return torch.float32
+    if out_dtype not in OUT_FORMATS:
+        raise TypeError(f"out_dtype must be None, torch.float32, torch.float16 or torch.bfloat16 (got {out_dtype!r})")
+    return out_dtype
 
 
 def convc1_mode(mode, presplit):

@@ -3,6 +3,7 @@
 Same constructor and call signatures as the reference:
     corr_fn = CorrBlock(fmap1, fmap2, num_levels=4, radius=4)      # corr.py:13  (eraft.py:107)
     corr    = corr_fn(coords1)                                       # corr.py:29  (eraft.py:128)
+    corr    = corr_fn(coords1, out_dtype=torch.float16)              # the same lookup, 16-bit elements
     CorrBlock.corr(fmap1, fmap2) -> [B, H, W, 1, H, W]               # corr.py:52
     corr_fn.corr_pyramid[i] : [B*H*W, 1, h_i, w_i]                   # corr.py:16,24,27
 The work happens in libecorr.so (hand-written gfx950 HIP kernels, C ABI include/ecorr.h): one
@@ -15,6 +16,14 @@ Contract differences, all loud: inputs must be fp32 HIP tensors (the reference p
 eraft.py:104-105); by default the block is forward-only (E-RAFT only ever calls it under
 torch.no_grad(), test.py:80) and refuses inputs that require grad while grad mode is on; coords
 must match the build's (B, 2, H, W) exactly.
+
+Mixed precision: `corr_fn(coords, out_dtype=torch.float16 | torch.bfloat16)` returns the lookup in
+that dtype (ecorr_lookup_as, csrc/lookup_half.hip): each element is the fp32 sample
+rounded once to nearest-even, bitwise `corr_fn(coords).to(dtype)`, stored by the lookup kernel itself
+-- half the output bytes and no cast kernel in front of an autocast convc1 (eraft.py:131-132).
+out_dtype None or torch.float32 is the fp32 call exactly; any other dtype raises TypeError.  On a
+differentiable block the 16-bit lookup is differentiable too: its backward converts the incoming
+gradient with .float() and runs the fp32 backward.  lookup_conv1x1_relu keeps its fp32 output.
 
 Training (opt-in): CorrBlock(fmap1, fmap2, num_levels, radius, differentiable=True) accepts fmaps
 that require grad and gives them gradients through the build and every `corr_fn(coords)` lookup
@@ -110,12 +119,12 @@ class _LookupFn(torch.autograd.Function):
     """(handle, coords) -> the lookup; backward adds into the block's gradient pyramid."""
 
     @staticmethod
-    def forward(ctx, handle, coords, state, pyramid):
+    def forward(ctx, handle, coords, state, pyramid, out_dtype=torch.float32):
         ctx.state = state
         ctx.save_for_backward(coords)   # versioned: an in-place change before backward raises
         B, _, H, W = state.shape
         K = 2 * state.radius + 1
-        out = torch.empty((B, state.levels * K * K, H, W), dtype=torch.float32, device=state.device)
+        out = torch.empty((B, state.levels * K * K, H, W), dtype=out_dtype, device=state.device)
         return _lib.lookup(pyramid, coords.contiguous(), (B, H, W), H * W, state.levels, state.radius, out,
                            "CorrBlock")
 
@@ -128,7 +137,7 @@ class _LookupFn(torch.autograd.Function):
                                "consumed (one backward per differentiable block)")
         (coords,) = ctx.saved_tensors
         B, _, H, W = st.shape
-        go = grad_out.contiguous()
+        go = grad_out.float().contiguous()   # a 16-bit lookup's gradient: the fp32 backward on its exact values
         cc = coords.contiguous()
         with _lib.on_device(st.device):
             if st.G is None:
@@ -136,7 +145,7 @@ class _LookupFn(torch.autograd.Function):
             _lib.check(_lib.lib().ecorr_lookup_backward(
                 go.data_ptr(), cc.data_ptr(), B, H, W, H * W, st.levels, st.radius, st.G.data_ptr(),
                 _lib.stream_of(go)), "CorrBlock lookup backward")
-            return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None
+            return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None, None
 
 
 class _LookupConvFn(torch.autograd.Function):
@@ -266,7 +275,11 @@ class CorrBlock:
             self._levels_cache = levels_of(self._pyramid, self._rows, self._shape[2], self._shape[3], self.num_levels)
         return self._levels_cache
 
-    def __call__(self, coords):
+    def __call__(self, coords, out_dtype=None):
+        """The lookup [B, num_levels * (2r+1)^2, H, W] (corr.py:29-50).  out_dtype: None / torch.float32
+        (the fp32 call), torch.float16 or torch.bfloat16 (the same launch storing each fp32 sample
+        rounded once to nearest-even: bitwise self(coords).to(out_dtype)); anything else: TypeError."""
+        out_dtype = _lib.lookup_out_dtype(out_dtype)
         B, _, H, W = self._shape
         _require_device_f32("coords", coords)
         if self._grad is not None and torch.is_grad_enabled() and coords.requires_grad:
@@ -279,10 +292,10 @@ class CorrBlock:
         if coords.device != self._device:
             raise RuntimeError("coords is on a different device than the pyramid")
         if self._grad is not None:
-            return _LookupFn.apply(self._handle, coords, self._grad, self._pyramid)
+            return _LookupFn.apply(self._handle, coords, self._grad, self._pyramid, out_dtype)
         coords = coords.contiguous()   # the reference accepts any strides (permute + reshape)
         K = 2 * self.radius + 1
-        out = torch.empty((B, self.num_levels * K * K, H, W), dtype=torch.float32, device=self._device)
+        out = torch.empty((B, self.num_levels * K * K, H, W), dtype=out_dtype, device=self._device)
         return _lib.lookup(self._pyramid, coords, (B, H, W), H * W, self.num_levels, self.radius, out, "CorrBlock")
 
     def lookup_conv1x1_relu(self, coords, weight, bias=None, mode=None):

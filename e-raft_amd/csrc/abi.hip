@@ -204,6 +204,16 @@ ECORR_EXPORT int ecorr_lookup(const float* pyramid, const float* coords, int B, 
     return launch_lookup(P, B, (hipStream_t)stream);
 }
 
+ECORR_EXPORT int ecorr_lookup_as(const float* pyramid, const float* coords, int B, int H, int W, int q_count,
+                                 int levels, int radius, int out_format, void* out, void* stream) {
+    LookupParams P{};
+    const int st = lookup_params(pyramid, coords, B, H, W, q_count, levels, radius, (float*)out, &P);
+    if (st != ECORR_OK) return st;
+    if (out_format != ECORR_OUT_F32 && out_format != ECORR_OUT_F16 && out_format != ECORR_OUT_BF16)
+        return ECORR_EINVAL;
+    return launch_lookup(P, B, (hipStream_t)stream, out_format);
+}
+
 ECORR_EXPORT int ecorr_lookup_qmax(const float* pyramid, const float* coords, int B, int H, int W, int q_count,
                                    int levels, int radius, float* out, float* qmax, void* stream) {
     if (!qmax) return ECORR_EINVAL;

@@ -83,7 +83,8 @@ int64_t build_split_workspace_bytes(int B, int D, int H, int W, int q_count);
 
 struct LookupParams : LevelTable<const float> {   // the table: the pyramid (read only)
     const float* coords;  // [B][2][q_count]
-    float* out;           // [B][C][q_count]
+    float* out;           // [B][C][q_count]; 2-byte elements in the same order when the launch's
+                          // out_format is ECORR_OUT_F16 / ECORR_OUT_BF16 (launch_lookup)
     int H, W;
     int q_count;
     int levels, radius;
@@ -94,7 +95,10 @@ struct LookupParams : LevelTable<const float> {   // the table: the pyramid (rea
                           // scale[b][q] the query's column exponent (launch_split_column_scale)
 };
 
-int launch_lookup(const LookupParams& P, int B, hipStream_t stream);
+// out_format: ECORR_OUT_* (include/ecorr.h); the 16-bit formats have no qmax / presplit form
+int launch_lookup(const LookupParams& P, int B, hipStream_t stream, int out_format = ECORR_OUT_F32);
+// lookup_half.hip: launch_lookup's paths with ECORR_OUT_F16 / ECORR_OUT_BF16 elements
+int launch_lookup_half(const LookupParams& P, int B, hipStream_t stream, int out_format);
 
 // grad.hip: the backward (ecorr_lookup_backward, ecorr_build_backward).  The gradient pyramid has the
 // pyramid's storage: the table is the gradient pyramid's.

@@ -15,6 +15,8 @@ Reference map:
     BasicMotionEncoder       update.py:63-81       SepConvGRU            update.py:33-60
     FlowHead                 update.py:6-14
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -193,14 +195,29 @@ class ERAFT(nn.Module):
     train_motion_corr=True is fuse_motion_corr on a differentiable CorrBlock: every iteration runs
     CorrBlock.lookup_conv1x1_relu in the forward and its HIP backward, so fnet and
     convc1 train through it; under torch.no_grad() its predictions are bitwise fuse_motion_corr's.
+    mixed_precision=True is the reference's mixed-precision path (eraft.py:101, 110-117, 131-132, which
+    its get_args() switches off): fnet, cnet and the update block run under
+    torch.autocast("cuda", dtype=amp_dtype) (torch.float16 or torch.bfloat16), the fmaps go back to
+    fp32 for the CorrBlock, coords and predictions stay fp32, and the lookup is asked for amp_dtype
+    directly (corr_fn(coords1, out_dtype=amp_dtype): the kernel stores what autocast's cast in front
+    of convc1 would produce, bit for bit).  It composes with fuse_motion_corr,
+    differentiable_corr and train_motion_corr (lookup_conv1x1_relu keeps its fp32 output);
+    hip_upsample gets the mask as fp32.  _native_half_lookup=False (private: the A/B arm of the tests
+    and tools/bench_lookup_half.py) takes the fp32 lookup and lets autocast cast it.
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
     corr_radius = 4
 
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
-                 differentiable_corr=False, train_motion_corr=False):
+                 differentiable_corr=False, train_motion_corr=False, mixed_precision=False,
+                 amp_dtype=torch.float16, _native_half_lookup=True):
         super().__init__()
+        if amp_dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError(f"amp_dtype must be torch.float16 or torch.bfloat16 (got {amp_dtype!r})")
+        self.mixed_precision = bool(mixed_precision)
+        self.amp_dtype = amp_dtype
+        self._native_half_lookup = bool(_native_half_lookup)
         if train_motion_corr:
             differentiable_corr = fuse_motion_corr = True
         elif differentiable_corr and fuse_motion_corr:
@@ -243,17 +260,28 @@ class ERAFT(nn.Module):
         up = torch.sum(m * nb, dim=2).permute(0, 1, 4, 2, 5, 3)
         return up.reshape(N, 2, 8 * H, 8 * W)
 
+    def _autocast(self):
+        """The reference's autocast(enabled=args.mixed_precision) (eraft.py:101, 110, 131); without
+        mixed_precision no context at all, so the default path is the one it always was."""
+        if not self.mixed_precision:
+            return contextlib.nullcontext()
+        return torch.autocast("cuda", dtype=self.amp_dtype)
+
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True):
         image1 = self.image_padder.pad(image1).contiguous()
         image2 = self.image_padder.pad(image2).contiguous()
-        fmap1, fmap2 = self.fnet([image1, image2])
+        with self._autocast():
+            fmap1, fmap2 = self.fnet([image1, image2])
         # differentiable_corr: gradients reach fnet through the HIP backward (corr.py); the keyword
         # is passed only then, so a reference-signature CorrBlock can stand in otherwise
         corr_fn = CorrBlock(fmap1.float().contiguous(), fmap2.float().contiguous(),
                             num_levels=self.corr_levels, radius=self.corr_radius,
                             **({"differentiable": True} if self.differentiable_corr else {}))
-        net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
-        net, inp = torch.tanh(net), torch.relu(inp)
+        with self._autocast():
+            net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
+            net, inp = torch.tanh(net), torch.relu(inp)
+        # mixed precision: the lookup stores amp_dtype itself, what autocast would cast it to for convc1
+        half_lookup = self.mixed_precision and self._native_half_lookup
         coords0, coords1 = self.initialize_flow(image1)
         if flow_init is not None:
             coords1 = coords1 + flow_init
@@ -263,11 +291,17 @@ class ERAFT(nn.Module):
             if self.fuse_motion_corr:
                 c1 = self.update_block.encoder.convc1
                 corr = corr_fn.lookup_conv1x1_relu(coords1, c1.weight, c1.bias)
+            elif half_lookup:
+                corr = corr_fn(coords1, out_dtype=self.amp_dtype)
             else:
                 corr = corr_fn(coords1)
-            net, up_mask, delta = self.update_block(net, inp, corr, coords1 - coords0,
-                                                    corr_is_convc1=self.fuse_motion_corr)
+            with self._autocast():
+                net, up_mask, delta = self.update_block(net, inp, corr, coords1 - coords0,
+                                                        corr_is_convc1=self.fuse_motion_corr)
             coords1 = coords1 + delta
-            up = (hip_upsample_flow if self.hip_upsample else self.upsample_flow)(coords1 - coords0, up_mask)
+            if self.hip_upsample:   # the HIP kernel takes fp32 (autocast's mask is amp_dtype)
+                up = hip_upsample_flow(coords1 - coords0, up_mask.float())
+            else:
+                up = self.upsample_flow(coords1 - coords0, up_mask)
             predictions.append(self.image_padder.unpad(up))
         return coords1 - coords0, predictions

@@ -222,7 +222,10 @@ class RowShardedCorrBlock:
         r0, rr = self.starts[self.rank], self.counts[self.rank]
         return self._local_coords(coords if rr == H else coords[:, :, r0:r0 + rr])
 
-    def __call__(self, coords):
+    def __call__(self, coords, out_dtype=None):
+        if _lib.lookup_out_dtype(out_dtype) != torch.float32:   # None / float32: the fp32 call, as CorrBlock
+            raise NotImplementedError(f"RowShardedCorrBlock: out_dtype={out_dtype} is not supported, the row exchange "
+                                      "carries fp32 lookups only; call it without out_dtype and cast the result")
         B, _, H, W = self._shape
         coords_rows = self._full_coords_rows(coords)
         K = 2 * self.radius + 1

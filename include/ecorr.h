@@ -106,6 +106,22 @@ int ecorr_build_split_gemm(int B, int D, int H, int W, int q_count, int levels, 
 int ecorr_lookup(const float* pyramid, const float* coords, int B, int H, int W, int q_count,
                  int levels, int radius, float* out, void* stream);
 
+/* ecorr_lookup with a chosen output element (added within ABI 17: purely additive, the version
+ * stays 17): out holds B*levels*(2r+1)^2*q_count elements of out_format in ecorr_lookup's order
+ * [B][C][q_count] -- float (ECORR_OUT_F32: ecorr_lookup's launch, bit for bit), IEEE binary16
+ * (ECORR_OUT_F16) or bfloat16 (ECORR_OUT_BF16), 2-byte aligned.  Rounding contract: the element is
+ * the fp32 sample ecorr_lookup computes, rounded ONCE to nearest-even -- binary16 as the hardware
+ * convert does (|x| past 65504 + half an ulp gives +-inf, subnormals are kept, NaN stays NaN);
+ * bfloat16 to nearest-even on the upper 16 bits (NaN stays NaN, +-inf stays +-inf) -- so it equals a
+ * cast of ecorr_lookup's output, which a mixed-precision consumer (autocast's convc1) would otherwise
+ * make in a kernel of its own.  Same argument validation and error codes as ecorr_lookup; an unknown
+ * out_format gives ECORR_EINVAL.  Replaces: corr.py:29-50 followed by autocast's cast (eraft.py:131-132). */
+#define ECORR_OUT_F32 0
+#define ECORR_OUT_F16 1
+#define ECORR_OUT_BF16 2
+int ecorr_lookup_as(const float* pyramid, const float* coords, int B, int H, int W, int q_count,
+                    int levels, int radius, int out_format, void* out, void* stream);
+
 /* ---- The backward (ABI 17): gradients of a loss through ecorr_lookup and ecorr_build, coordinates detached ----
  * Deterministic: a query row's gradient images are owned by one workgroup per launch and summed in
  * a fixed order; there are no float atomics, so equal inputs give bitwise equal gradients. */

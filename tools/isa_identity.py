@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Are the kernels two source trees have in common the same gfx950 instructions?
 
-    python tools/isa_identity.py BEFORE_CSRC AFTER_CSRC [file.hip ...] > profiles/<topic>/isa_identity.txt
+    python tools/isa_identity.py [--renamed REGEX=REPL ...] BEFORE_CSRC AFTER_CSRC [file.hip ...] \
+        > profiles/<topic>/isa_identity.txt
 
 BEFORE_CSRC / AFTER_CSRC: two copies of e-raft_amd/csrc (each beside its ../../include, e.g. a
 `git worktree` of the parent commit and the working tree).  Every listed source (default: all of
@@ -10,6 +11,11 @@ code-generation flags to assembly; per kernel the instruction stream (no directi
 in local labels `.LBB<n>_` dropped, as a kernel added earlier in the file shifts it) and the
 resource block (VGPRs, LDS, scratch) are compared.  One line per kernel: identical / DIFFERS /
 only-before / only-after; exit status 1 when a common kernel differs.  CPU only (hipcc -S).
+
+--renamed REGEX=REPL (repeatable): a kernel of AFTER whose mangled name is absent in BEFORE is
+compared with the BEFORE kernel named re.sub(REGEX, REPL, name), when that exists -- for a kernel
+whose name changed but whose code must not have, e.g. an instantiation that gained a defaulted
+template parameter (`Li0E` appended to its argument list).  Such a line names both kernels.
 """
 import os
 import re
@@ -50,15 +56,34 @@ def kernels(csrc, src, tmp):
 
 
 def main():
-    before, after, only = sys.argv[1], sys.argv[2], sys.argv[3:]
+    args, renames = sys.argv[1:], []
+    while args and args[0] == "--renamed":
+        pat, repl = args[1].split("=", 1)
+        renames.append((re.compile(pat), repl))
+        args = args[2:]
+    before, after, only = args[0], args[1], args[2:]
     srcs = only or sources(after)
     bad = 0
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         for src in srcs:
             a = kernels(before, src, ta) if os.path.exists(os.path.join(before, src)) else {}   # a new file
             b = kernels(after, src, tb)
-            for name in sorted(set(a) | set(b)):
-                if name not in b:
+            was = {}   # AFTER name -> its BEFORE name, for the renamed kernels
+            for name in b:
+                if name not in a:
+                    for pat, repl in renames:
+                        old = pat.sub(repl, name)
+                        if old != name and old in a and old not in b:
+                            was[name] = old
+                            break
+            for name in sorted((set(a) - set(was.values())) | set(b)):
+                if name in was:
+                    ins, v, l, sc = b[name]
+                    same = a[was[name]] == b[name]
+                    bad += not same
+                    print(f"{src} {name} (before: {was[name]}): {len(ins)} instr, {v} vgpr, {l} lds, {sc} scratch, "
+                          + ("identical" if same else "DIFFERS"))
+                elif name not in b:
                     print(f"{src} {name}: only-before")
                 elif name not in a:
                     ins, v, l, sc = b[name]

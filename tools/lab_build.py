@@ -42,7 +42,7 @@ PATCHES["loopprio"] = [("build.hip", "    TFrags fa, fb;\n", "    __builtin_amdg
                        ("build.hip", EPI, EPI + "    __builtin_amdgcn_s_setprio(0);\n")]
 PATCHES["loopprio3"] = [("build.hip", "    TFrags fa, fb;\n", "    __builtin_amdgcn_s_setprio(3);\n    TFrags fa, fb;\n"),
                         ("build.hip", EPI, EPI + "    __builtin_amdgcn_s_setprio(0);\n")]
-PATCHES["lk_noblend"] = [("lookup.hip", "                const float v = blend(c[0], c[1], c[SW], c[SW + 1], wx[ai], wy[bb]);",
+PATCHES["lk_noblend"] = [("lookup_kernels.h", "                const float v = blend(c[0], c[1], c[SW], c[SW + 1], wx[ai], wy[bb]);",
                           "                const float v = c[0];")]
 # tile order: m-tiles per group of the grouped order (tree: 8)
 # split16 tile-group bound (balanced groups since round 5; the round-4/5 records of gm2/4/16 were
@@ -193,12 +193,12 @@ PATCHES["qsnost"] = PATCHES["qs"] + [
 # the tree as it is (the baseline of an A/B against an edited tree)
 PATCHES["base"] = []
 # lookup windows staged one column per work item (b32 loads) instead of 8-byte column pairs
-PATCHES["nopair"] = [("lookup.hip", "        bool pair = true;", "        bool pair = false;")]
+PATCHES["nopair"] = [("lookup_kernels.h", "    *pair = true;", "    *pair = false;")]
 # timing only: no window loads for one level (what does each level's staging cost?)
 for _lv in range(4):
     PATCHES[f"lk_skip{_lv}"] = [("lookup_stage.h", "            const bool need = (unsigned)(ry - rlo) < (unsigned)(rhi - rlo);",
                                  f"            const bool need = lv != {_lv} && (unsigned)(ry - rlo) < (unsigned)(rhi - rlo);")]
-PATCHES["lk_prio2"] = [("lookup.hip", "    if (md == 0) {\n        int yo[K];", "    __builtin_amdgcn_s_setprio(2);\n    if (md == 0) {\n        int yo[K];")]
+PATCHES["lk_prio2"] = [("lookup_kernels.h", "    if (md == 0) {\n        int yo[K];", "    __builtin_amdgcn_s_setprio(2);\n    if (md == 0) {\n        int yo[K];")]
 PATCHES["nopairm"] = [("motion.hip", "    bool pair = true;", "    bool pair = false;")]
 # fused lookup + convc1 ablations (timing only, AB_NOCHECK=1): no GEMM phase / no lookup phase
 PATCHES["mo_nogemm"] = [("motion.hip", "    for (int oc = 0; oc < O; oc += OB) {", "    for (int oc = 0; oc < 0; oc += OB) {")]
@@ -502,22 +502,22 @@ PATCHES["mo_wsst"] = [
 PATCHES["cv_bnt"] = [("conv.hip", "v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(csrc, off + j * qs, 0, 0));",
                       "v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(csrc, off + j * qs, 0, 2));")]
 # the QMAX lookup's output stores with sc1 (16) / nt | sc1 (18) instead of the default policy
-PATCHES["lk_qsc1"] = [("lookup.hip", "constexpr int kOutAux = QMAX ? 0 : 2;", "constexpr int kOutAux = QMAX ? 16 : 2;")]
-PATCHES["lk_qntsc1"] = [("lookup.hip", "constexpr int kOutAux = QMAX ? 0 : 2;", "constexpr int kOutAux = QMAX ? 18 : 2;")]
+PATCHES["lk_qsc1"] = [("lookup_kernels.h", "constexpr int kOutAux = QMAX ? 0 : 2;", "constexpr int kOutAux = QMAX ? 16 : 2;")]
+PATCHES["lk_qntsc1"] = [("lookup_kernels.h", "constexpr int kOutAux = QMAX ? 0 : 2;", "constexpr int kOutAux = QMAX ? 18 : 2;")]
 # lookup_cols_reg dispatch order: all level-0 workgroups first (the longest: the largest image),
 # then levels 1..3 fill the last round (LPT for the drain tail) -- or the reverse
 _LK_OLD = """    const int lv = blockIdx.y, b = blockIdx.z;
     const int q0 = blockIdx.x * QB;
     const int p = q0 + g;"""
 def _lk_lvmajor(rev):
-    return [("lookup.hip", _LK_OLD, """    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    return [("lookup_kernels.h", _LK_OLD, """    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     const int per = gridDim.x * gridDim.z;
     const int lvo = lin / per, rr = lin - lvo * per;
     const int lv = %s, b = rr / gridDim.x;
     const int q0 = (rr - b * gridDim.x) * QB;
     const int p = q0 + g;""" % ("gridDim.y - 1 - lvo" if rev else "lvo"))]
 # ... or the level fastest: a query group's four level workgroups dispatched back to back
-PATCHES["lk_lvminor"] = [("lookup.hip", _LK_OLD, """    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+PATCHES["lk_lvminor"] = [("lookup_kernels.h", _LK_OLD, """    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     const int lv = lin % gridDim.y, xb = lin / gridDim.y;
     const int b = xb / gridDim.x;
     const int q0 = (xb - b * gridDim.x) * QB;
@@ -544,7 +544,7 @@ PATCHES["cv_pf4"] = [("conv.hip", "constexpr int kConvPD = 2;", "constexpr int k
 # instead of 5 (timing only, bitwise the same); and de-phased first rounds (a share of the first
 # 1280 workgroups sleeps ~3.8 / ~1.9 us before its coordinate loads)
 def _lk_pad(nf):
-    return [("lookup.hip", """    __shared__ WB st;
+    return [("lookup_kernels.h", """    __shared__ WB st;
     const int tid = threadIdx.x, g = tid % QB;
     const int part = __builtin_amdgcn_readfirstlane(tid / QB);   // wave-uniform""", """    __shared__ WB st;
     __shared__ float lk_pad[%d];
@@ -554,7 +554,7 @@ def _lk_pad(nf):
 PATCHES["lk_occ4"] = _lk_pad(2048)
 PATCHES["lk_occ3"] = _lk_pad(5000)
 def _lk_sleep(n, mod):
-    return [("lookup.hip", """    __shared__ WB st;
+    return [("lookup_kernels.h", """    __shared__ WB st;
     const int tid = threadIdx.x, g = tid % QB;
     const int part = __builtin_amdgcn_readfirstlane(tid / QB);   // wave-uniform""", """    __shared__ WB st;
     {
@@ -570,8 +570,8 @@ PATCHES["lk_sleep64"] = _lk_sleep(64, 2)
 # the output stores out of range (no memory traffic; timing only)
 PATCHES["lk_ldoob"] = [("lookup_stage.h", "__builtin_amdgcn_raw_buffer_load_b64(rsrc, need ? off : OOB, 0, 0);",
                         "__builtin_amdgcn_raw_buffer_load_b64(rsrc, need ? OOB : OOB + (off & 4), 0, 0);")]
-PATCHES["lk_stoob"] = [("lookup.hip", "P.out + (int64_t)b * P.C * P.q_count, 0, P.C * P.q_count * 4, 0x00020000);",
-                        "P.out + (int64_t)b * P.C * P.q_count, 0, P.q_count == -1 ? 4 : 0, 0x00020000);")]
+PATCHES["lk_stoob"] = [("lookup_kernels.h", "reinterpret_cast<OT*>(P.out) + (int64_t)b * P.C * P.q_count, 0, P.C * P.q_count * ES, 0x00020000);",
+                        "reinterpret_cast<OT*>(P.out) + (int64_t)b * P.C * P.q_count, 0, P.q_count == -1 ? 4 : 0, 0x00020000);")]
 COMBOS["lk_bothoob"] = ["lk_ldoob", "lk_stoob"]
 
 # the same on lookup_win (round 5)
@@ -630,7 +630,7 @@ PATCHES["sp_stamps"] = [
 # all 81 channels of a level write one 256-B piece per workgroup) -- do the output writes cost the
 # window reads their cache hits?  And window loads all from the first query group's slab (every
 # workgroup reads the same lines: L2 hits)
-PATCHES["lk_stsmall"] = [("lookup.hip", "sbase + (a * K + bb) * P.q_count * 4, kOutAux);", "sbase * 0 + ((a * K + bb) & 0), kOutAux);")]
+PATCHES["lk_stsmall"] = [("lookup_kernels.h", "sbase + (a * K + bb) * P.q_count * ES);", "sbase * 0 + ((a * K + bb) & 0));")]
 PATCHES["lk_ldsmall"] = [("lookup_stage.h", "    const int64_t R0 = (int64_t)b * P.q_count + q0;   // first query row of the group",
                           "    const int64_t R0 = 0 * ((int64_t)b * P.q_count + q0);   // (lab: every group reads group 0)")]
 COMBOS["lk_bothsmall"] = ["lk_stsmall", "lk_ldsmall"]
@@ -639,10 +639,10 @@ COMBOS["lk_bothsmall"] = ["lk_stsmall", "lk_ldsmall"]
 # (same bytes, same store instructions, a wrong layout) -- does the NCHW output's 256-B-per-row
 # scatter cost the write stream?
 PATCHES["lk_stblock"] = [
-    ("lookup.hip", "    const int voff = p * 4;\n    const int sbase = lv * KK * P.q_count * 4;",
-     "    const int voff = g * 4;\n    const int sbase = (blockIdx.x + gridDim.x * lv) * KK * 256;"),
-    ("lookup.hip", "sbase + (a * K + bb) * P.q_count * 4, kOutAux);", "sbase + (a * K + bb) * 256, kOutAux);"),
-    ("lookup.hip", "sbase + ((part * AP + ai) * K + bb) * P.q_count * 4, kOutAux);", "sbase + ((part * AP + ai) * K + bb) * 256, kOutAux);")]
+    ("lookup_kernels.h", "    const int voff = p * ES;\n    const int sbase = lv * KK * P.q_count * ES;",
+     "    const int voff = g * ES;\n    const int sbase = (blockIdx.x + gridDim.x * lv) * KK * 64 * ES;"),
+    ("lookup_kernels.h", "sbase + (a * K + bb) * P.q_count * ES);", "sbase + (a * K + bb) * 64 * ES);"),
+    ("lookup_kernels.h", "sbase + ((part * AP + ai) * K + bb) * P.q_count * ES);", "sbase + ((part * AP + ai) * K + bb) * 64 * ES);")]
 
 # ---- round 5, split convc1: what bounds conv1x1_split_kernel (timing only)?  Every workgroup reads
 # batch item 0's first 64 query columns (the corr stream served by L2), and / or every output store
