@@ -1,0 +1,50 @@
+"""Shared helpers of the bit-exact kernel tests (test infrastructure; torch only inside guarded()).
+
+guarded / check_guarded: an output handed to a kernel lies in the middle of a buffer filled with one
+bit pattern, GUARD floats of it on each side: a store outside the output changes a guard band, an
+element the kernel never wrote keeps the pattern.
+mismatch: the text of a failed bitwise comparison.
+GRID_STRIDE_THREADS: the threads of one pass of the generic kernels' grid-stride loops.
+"""
+import numpy as np
+
+GUARD = 64            # floats on each side of an output (256 bytes: the output keeps its alignment)
+FILL = 0x7b7b7b7b     # 1.3e36 as a float: finite, not NaN, and nothing the kernels under test compute
+GRID_STRIDE_THREADS = 8192 * 256   # grid_for() (csrc/lookup_kernels.h): at most 8192 blocks of NT = 256 threads
+
+
+def guarded(n, device="cuda"):
+    """(the whole int32 buffer, its middle n elements as float32), FILL everywhere."""
+    import torch
+    buf = torch.full((n + 2 * GUARD,), FILL, dtype=torch.int32, device=device)
+    return buf, buf[GUARD:GUARD + n].view(torch.float32)
+
+
+def check_guarded(buf, what):
+    """Asserts the guards untouched and no element of the middle left unwritten -> the middle as
+    numpy float32."""
+    host = buf.cpu().numpy()
+    assert (host[:GUARD] == FILL).all() and (host[-GUARD:] == FILL).all(), f"{what}: a guard band was written"
+    mid = host[GUARD:-GUARD]
+    left = int((mid == FILL).sum())
+    assert left == 0, f"{what}: {left} of {mid.size} elements were never written"
+    return mid.view(np.float32)
+
+
+def mismatch(got, want):
+    """None when got and want ([B, C, ...] float32) are the same bits up to NaN payloads
+    (oracle.same_bits), else a text: the count of differing elements and the first one's
+    (b, channel, query) with both values."""
+    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
+    if got.shape != want.shape:
+        return f"shape {got.shape} != {want.shape}"
+    ng, nw = np.isnan(got), np.isnan(want)
+    bad = (ng != nw) | (~ng & ~nw & (got.view(np.uint32) != want.view(np.uint32)))
+    n = int(bad.sum())
+    if n == 0:
+        return None
+    B, C = got.shape[:2]
+    b, c, q = np.argwhere(bad.reshape(B, C, -1))[0]
+    g, w = got.reshape(B, C, -1)[b, c, q], want.reshape(B, C, -1)[b, c, q]
+    return (f"{n} of {bad.size} elements differ; first at (b, channel, query) = ({b}, {c}, {q}): got {g!r} "
+            f"({g.view(np.uint32):#010x}), expected {w!r} ({w.view(np.uint32):#010x})")

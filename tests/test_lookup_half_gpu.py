@@ -19,7 +19,9 @@ Each case runs four coordinate sets -- smooth (prng.coords_with_flow), grad_ref.
 four borders) and i.i.d. large flows -- so all three modes of the radius-4 kernel occur: window
 (md 0), direct gather (md 1: the special queries) and past the range (md 2: the lanes of the tail
 block).  From the fp32 output, which no new code produced, each case asserts that NaN, exact zero
-(taps outside the image) and non-zero finite values are all present.
+(taps outside the image) and non-zero finite values are all present.  That fp32 reference is itself
+checked against the oracle, bit for bit: at radius 4 by tests/test_corr_gpu.py, at radii 0, 1, 2, 3
+and 5 (these shapes among others) by tests/test_lookup_radius_gpu.py.
 """
 import numpy as np
 import pytest
