@@ -6,6 +6,10 @@ kernels run in torch's HIP context on torch's streams and caching-allocator poin
 
 There is no fallback: if libecorr.so is missing or was built for another target, every entry point
 raises.  Build it with `make -C e-raft_amd/csrc` or `python -c "import __graft_entry__ as g; g.build()"`.
+
+What every wrapper in the package is made of, each defined here once: require_device (the argument
+check), ptr (an optional tensor as a pointer), scratch (size entry -> temporary), on_device (the
+device context of a launch), stream_of, check, corr_channels.
 """
 import contextlib
 import ctypes
@@ -166,19 +170,46 @@ def check(status: int, what: str):
     raise RuntimeError(msg)
 
 
-def _require_device_f32(name, t):
+def require_device(name, t, dtype=torch.float32):
+    """The argument check of every entry that takes tensors: a HIP tensor of `dtype`."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if t.device.type != "cuda":
         raise RuntimeError(f"{name} is on {t.device}: eraft_amd runs only on HIP devices (no CPU path)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32 (got {t.dtype})")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {str(dtype).removeprefix('torch.')} (got {t.dtype})")
 
 
-def _no_grad_inputs(*ts):
+def no_grad_inputs(*ts):
     if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
         raise RuntimeError("eraft_amd CorrBlock is forward-only; call it under torch.no_grad() "
                            "(as the reference harness does, test.py:80)")
+
+
+def require_fmap_pair(fmap1, fmap2, differentiable=False):
+    """The fmap checks of CorrBlock and RowShardedCorrBlock.  Returns whether the gradient path is live:
+    asked for (differentiable) and needed; otherwise fmaps that require grad raise."""
+    require_device("fmap1", fmap1)
+    require_device("fmap2", fmap2)
+    live = differentiable and torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
+    if not live:
+        no_grad_inputs(fmap1, fmap2)
+    if fmap1.dim() != 4 or fmap1.shape != fmap2.shape:
+        raise RuntimeError(f"fmap shapes {tuple(fmap1.shape)} / {tuple(fmap2.shape)} differ "
+                           "or are not [B, D, H, W]")
+    if fmap1.device != fmap2.device:
+        raise RuntimeError("fmap1 and fmap2 are on different devices")
+    return live
+
+
+def ptr(t):
+    """An optional tensor as a pointer argument: None (NULL) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def corr_channels(levels: int, radius: int) -> int:
+    """Channels of a lookup: levels * (2r+1)^2."""
+    return levels * (2 * radius + 1) ** 2
 
 
 def layout(rows: int, H: int, W: int, levels: int):
@@ -207,9 +238,29 @@ _same_device = contextlib.nullcontext()
 
 
 def on_device(dev: torch.device):
-    """torch.cuda.device(dev) only when dev is not already current: the launches then go to dev's
-    context, and the per-call host cost stays off the lookup path (12 calls per pair)."""
+    """The device context of every launch in the package, entered only when dev is not already current:
+    the launches then go to dev's context, and the per-call host cost stays off the lookup path
+    (12 calls per pair)."""
     return _same_device if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+
+
+_scratch_sizes = {}   # (size entry, dims) -> what it answered: the size entries are pure functions of their integers
+
+
+def scratch(entry, *dims, device, what, dtype=torch.uint8, min_bytes=0):
+    """A temporary from the caching allocator (released stream-ordered after its last launch) of the
+    size that the library's size entry `entry` gives for the integers `dims`: bytes as uint8, or
+    elements of `dtype` where the entry counts those.  None when that is 0 (ptr() makes it NULL);
+    min_bytes=1 for an entry whose kernel wants a pointer anyway.  what: the text of a failure."""
+    n = _scratch_sizes.get((entry, dims))
+    if n is None:
+        size = _i64()
+        check(getattr(lib(), entry)(*dims, ctypes.byref(size)), what)
+        if len(_scratch_sizes) >= 4096:   # event counts differ from call to call (voxel grids): stay bounded
+            _scratch_sizes.clear()
+        n = _scratch_sizes[(entry, dims)] = size.value
+    n = max(n, min_bytes)
+    return torch.empty(n, dtype=dtype, device=device) if n > 0 else None
 
 
 # Which GEMM builds level 0 (include/ecorr.h): "split" = ecorr_build_split (f16 matrix cores on
@@ -252,9 +303,7 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
     pyr = torch.empty(off[-1], dtype=torch.float32, device=fmap2.device)
     st = stream_of(fmap2)
     if mode == "split":
-        nbytes = _i64()
-        check(lib().ecorr_build_split_workspace_size(B, D, H, W, q_count, ctypes.byref(nbytes)), what)
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=fmap2.device)
+        ws = scratch("ecorr_build_split_workspace_size", B, D, H, W, q_count, device=fmap2.device, what=what)
         tm = stage_events
         if tm is not None:   # bench.py: HIP events on this stream around the two stages
             mk = stage_event or (lambda: torch.cuda.Event(enable_timing=True))
@@ -286,36 +335,33 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
 # version counter; a change through .data that keeps all three (w.data.mul_(...)) between two calls
 # of ONE block is not seen -- weights are fixed during a forward.  The pack runs on the consumer's
 # stream `st`, so the lookups that read it are ordered after it.
+# kind: (size entry, pack entry, their two integers from (O, C), the weight transposed, the pack's element, label);
+# the fused pack is sized in floats, the others in bytes; the presplit pack's columns are in the
+# presplit corr's channel order (C = 81 * levels) and it takes the levels
+_PACKS = {
+    "fused": ("ecorr_conv1x1_packed_size", "ecorr_conv1x1_pack", lambda O, C: (O, C), False, torch.float32,
+              "convc1 weight pack"),
+    "split": ("ecorr_conv1x1_split_size", "ecorr_conv1x1_split_pack", lambda O, C: (O, C), False, torch.uint8,
+              "convc1 split weight pack"),
+    "split_t": ("ecorr_conv1x1_split_size", "ecorr_conv1x1_split_pack", lambda O, C: (C, O), True, torch.uint8,
+                "convc1 transposed weight pack"),
+    "presplit": ("ecorr_conv1x1_presplit_size", "ecorr_conv1x1_split_pack_presplit", lambda O, C: (O, C // 81), False,
+                 torch.uint8, "convc1 presplit weight pack"),
+}
+
+
 def packed_conv1x1_weight(weight, O, C, kind, st, cache):
     version = tensor_version(weight)
     key = (kind, O, C)
     ent = cache.get(key)
     if ent is not None and ent[0] is weight and ent[1] == (weight.data_ptr(), version):
         return ent[2]
+    size_entry, pack_entry, dims, transposed, dtype, label = _PACKS[kind]
     wt = weight.reshape(O, C).contiguous()
-    n = ctypes.c_int64()
-    if kind == "split_t":   # the transposed weight [C][O] in the split pack: grad_in of the backward
+    if transposed:
         wt = wt.t().contiguous()
-        check(lib().ecorr_conv1x1_split_size(C, O, ctypes.byref(n)), "convc1 transposed weight pack")
-        packed = torch.empty(n.value, dtype=torch.uint8, device=weight.device)
-        check(lib().ecorr_conv1x1_split_pack(wt.data_ptr(), C, O, packed.data_ptr(), st),
-              "convc1 transposed weight pack")
-    elif kind in ("split", "presplit"):
-        if kind == "split":
-            check(lib().ecorr_conv1x1_split_size(O, C, ctypes.byref(n)), "convc1 split weight pack")
-        else:
-            check(lib().ecorr_conv1x1_presplit_size(O, C // 81, ctypes.byref(n)), "convc1 presplit weight pack")
-        packed = torch.empty(n.value, dtype=torch.uint8, device=weight.device)
-        if kind == "split":
-            check(lib().ecorr_conv1x1_split_pack(wt.data_ptr(), O, C, packed.data_ptr(), st),
-                  "convc1 split weight pack")
-        else:   # the columns in the presplit corr's channel order (C = 81 * levels)
-            check(lib().ecorr_conv1x1_split_pack_presplit(wt.data_ptr(), O, C // 81, packed.data_ptr(), st),
-                  "convc1 presplit weight pack")
-    else:
-        check(lib().ecorr_conv1x1_packed_size(O, C, ctypes.byref(n)), "convc1 weight pack")
-        packed = torch.empty(n.value, dtype=torch.float32, device=weight.device)
-        check(lib().ecorr_conv1x1_pack(wt.data_ptr(), O, C, packed.data_ptr(), st), "convc1 weight pack")
+    packed = scratch(size_entry, *dims(O, C), device=weight.device, what=label, dtype=dtype)
+    check(getattr(lib(), pack_entry)(wt.data_ptr(), *dims(O, C), packed.data_ptr(), st), label)
     cache[key] = (weight, (weight.data_ptr(), version), packed)
     return packed
 
@@ -366,23 +412,22 @@ def lookup_conv1x1_relu(pyramid, coords, shape, q_count, levels, radius, weight,
     cannot give them (then, as for another radius or more levels: "split")."""
     B, H, W = shape
     dev = pyramid.device
-    _require_device_f32("weight", weight)
-    _no_grad_inputs(weight, *(() if bias is None else (bias,)))
+    require_device("weight", weight)
+    no_grad_inputs(weight, *(() if bias is None else (bias,)))
     if weight.device != dev or (bias is not None and bias.device != dev):
         raise RuntimeError("weight / bias are on a different device than the pyramid")
-    K = 2 * radius + 1
-    C = levels * K * K
+    C = corr_channels(levels, radius)
     O = weight.shape[0]
     if weight.numel() != O * C:
         raise RuntimeError(f"weight {tuple(weight.shape)} does not map {C} correlation channels")
     if bias is not None:
-        _require_device_f32("bias", bias)
+        require_device("bias", bias)
         if bias.numel() != O:
             raise RuntimeError(f"bias has {bias.numel()} elements, expected {O}")
         bias = bias.contiguous()
     if mode == "fused" and (O <= 0 or O % 64 != 0):
         raise RuntimeError(f"{O} output channels: the fused kernel needs a positive multiple of 64")
-    bptr = None if bias is None else bias.data_ptr()
+    bptr = ptr(bias)
     with on_device(dev):
         out = alloc_out(O)
         st = stream_of(out)
@@ -392,9 +437,7 @@ def lookup_conv1x1_relu(pyramid, coords, shape, q_count, levels, radius, weight,
                 mode = "split"
         wt = packed_conv1x1_weight(weight, O, C, mode, st, cache)   # once per block
         if mode == "presplit":
-            nbytes = ctypes.c_int64()
-            check(lib().ecorr_presplit_size(B, levels, q_count, ctypes.byref(nbytes)), f"{what} presplit size")
-            corr = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            corr = scratch("ecorr_presplit_size", B, levels, q_count, device=dev, what=f"{what} presplit size")
             check(lib().ecorr_lookup_presplit(
                 pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, scale.data_ptr(),
                 corr.data_ptr(), st), f"{what} lookup (presplit convc1)")
@@ -430,17 +473,12 @@ def conv1x1_relu_backward(grad_out, out, corr, weight, cache, want_in, want_weig
     dev = out.device
     with on_device(dev):
         st = stream_of(out)
-        nbytes = _i64()
-        check(lib().ecorr_conv1x1_relu_backward_workspace_size(B, C, Q, O, ctypes.byref(nbytes)), what)
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws = scratch("ecorr_conv1x1_relu_backward_workspace_size", B, C, Q, O, device=dev, what=what)
         pk = packed_conv1x1_weight(weight, O, C, "split_t", st, cache) if want_in else None
         gi = torch.empty((B, C) + tuple(out.shape[2:]), dtype=torch.float32, device=dev) if want_in else None
         gw = torch.empty(weight.shape, dtype=torch.float32, device=dev) if want_weight else None
         gb = torch.empty(O, dtype=torch.float32, device=dev) if want_bias else None
-
-        def ptr(t):
-            return None if t is None else t.data_ptr()
         check(lib().ecorr_conv1x1_relu_backward(
             grad_out.data_ptr(), out.data_ptr(), ptr(corr) if want_weight else None, ptr(pk), B, C, Q, O,
-            ptr(gi), ptr(gw), ptr(gb), ws.data_ptr(), st), what)
+            ptr(gi), ptr(gw), ptr(gb), ptr(ws), st), what)
     return gi, gw, gb

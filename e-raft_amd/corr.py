@@ -27,7 +27,7 @@ gradient with .float() and runs the fp32 backward.  lookup_conv1x1_relu keeps it
 
 Training (opt-in): CorrBlock(fmap1, fmap2, num_levels, radius, differentiable=True) accepts fmaps
 that require grad and gives them gradients through the build and every `corr_fn(coords)` lookup
-(ecorr_lookup_backward / ecorr_build_backward, csrc/grad.hip).  The forward runs
+(the two backward entries of csrc/grad.hip).  The forward runs
 the same launches, so its values are bitwise the plain block's; under torch.no_grad(), or when no
 fmap requires grad, the block is the plain block.  Autograd never carries a pyramid-sized tensor:
 the build is a Function of the fmaps returning a one-element handle, each lookup a Function of
@@ -48,7 +48,7 @@ weight, bias and its own output; the backward (ecorr_conv1x1_relu_backward, csrc
 DESIGN.md §3.3.1) masks the incoming gradient with the saved output, recomputes the lookup for the
 weight gradient instead of keeping it alive (99.5 MB per iteration at DSEC B = 16), runs grad_corr on
 the f16 matrix cores (the split conv with the transposed weight, packed once per block) and feeds it
-to ecorr_lookup_backward when the block is live.  With frozen fmaps only weight and bias receive
+to the lookup backward when the block is live.  With frozen fmaps only weight and bias receive
 gradients and no gradient pyramid is allocated.  Deterministic (no atomics).
 
 Numerics: the default build sums each product as f16 lo*hi + hi*lo + hi*hi of per-pixel-scaled
@@ -67,7 +67,7 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import _no_grad_inputs, _require_device_f32
+from ._lib import no_grad_inputs, require_device
 from .layout import levels_of
 
 
@@ -80,6 +80,23 @@ class _GradState:
         self.shape, self.levels, self.radius, self.numel, self.device = shape, levels, radius, numel, device
         self.G = None
         self.consumed = False
+
+    def require_unconsumed(self):
+        if self.consumed:
+            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
+                               "consumed (one backward per differentiable block)")
+
+    def add_lookup_grad(self, grad, coords):
+        """The one place a lookup's gradient enters G: grad (contiguous fp32 [B, C, H, W]) at contiguous
+        coords, on grad's current stream; G is allocated and zeroed by the first call.  The caller
+        holds the device (on_device) and returns the handle's gradient, a zero, itself: the two
+        lookup Functions make it at different points of their launch sequences."""
+        B, _, H, W = self.shape
+        if self.G is None:
+            self.G = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().ecorr_lookup_backward(
+            grad.data_ptr(), coords.data_ptr(), B, H, W, H * W, self.levels, self.radius, self.G.data_ptr(),
+            _lib.stream_of(grad)), "CorrBlock lookup backward")
 
 
 class _BuildFn(torch.autograd.Function):
@@ -95,9 +112,7 @@ class _BuildFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, _grad_handle):
         st = ctx.state
-        if st.consumed:
-            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
-                               "consumed (one backward per differentiable block)")
+        st.require_unconsumed()
         st.consumed = True
         f1, f2 = ctx.saved_tensors
         B, D, H, W = st.shape
@@ -110,8 +125,7 @@ class _BuildFn(torch.autograd.Function):
                 return (None if g1 is None else g1.zero_(), None if g2 is None else g2.zero_(), None)
             _lib.check(_lib.lib().ecorr_build_backward(
                 G.data_ptr(), f1.data_ptr(), f2.data_ptr(), B, D, H, W, H * W, st.levels,
-                None if g1 is None else g1.data_ptr(), None if g2 is None else g2.data_ptr(),
-                _lib.stream_of(f1)), "CorrBlock build backward")
+                _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(f1)), "CorrBlock build backward")
         return g1, g2, None
 
 
@@ -123,8 +137,8 @@ class _LookupFn(torch.autograd.Function):
         ctx.state = state
         ctx.save_for_backward(coords)   # versioned: an in-place change before backward raises
         B, _, H, W = state.shape
-        K = 2 * state.radius + 1
-        out = torch.empty((B, state.levels * K * K, H, W), dtype=out_dtype, device=state.device)
+        out = torch.empty((B, _lib.corr_channels(state.levels, state.radius), H, W), dtype=out_dtype,
+                          device=state.device)
         return _lib.lookup(pyramid, coords.contiguous(), (B, H, W), H * W, state.levels, state.radius, out,
                            "CorrBlock")
 
@@ -132,19 +146,12 @@ class _LookupFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         st = ctx.state
-        if st.consumed:
-            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
-                               "consumed (one backward per differentiable block)")
+        st.require_unconsumed()
         (coords,) = ctx.saved_tensors
-        B, _, H, W = st.shape
         go = grad_out.float().contiguous()   # a 16-bit lookup's gradient: the fp32 backward on its exact values
         cc = coords.contiguous()
         with _lib.on_device(st.device):
-            if st.G is None:
-                st.G = torch.zeros(st.numel, dtype=torch.float32, device=st.device)
-            _lib.check(_lib.lib().ecorr_lookup_backward(
-                go.data_ptr(), cc.data_ptr(), B, H, W, H * W, st.levels, st.radius, st.G.data_ptr(),
-                _lib.stream_of(go)), "CorrBlock lookup backward")
+            st.add_lookup_grad(go, cc)
             return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None, None
 
 
@@ -155,11 +162,7 @@ class _LookupConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, handle, coords, weight, bias, blk, mode):
-        B, _, H, W = blk._shape
-        out = _lib.lookup_conv1x1_relu(
-            blk._pyramid, coords.contiguous(), (B, H, W), H * W, blk.num_levels, blk.radius, weight, bias, mode,
-            lambda O: torch.empty((B, O, H, W), dtype=torch.float32, device=blk._device), blk._wcache, "CorrBlock",
-            column_scale=blk._column_scale)
+        out = blk._lookup_conv(coords, weight, bias, mode)
         # what the backward reads of the block, not the block: the pyramid, the geometry, the shared
         # gradient state (None: not live) and the packed-weight cache
         ctx.pyramid, ctx.state, ctx.wcache = blk._pyramid, blk._grad, blk._wcache
@@ -171,9 +174,8 @@ class _LookupConvFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         st = ctx.state
-        if st is not None and st.consumed:
-            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
-                               "consumed (one backward per differentiable block)")
+        if st is not None:
+            st.require_unconsumed()
         coords, out, weight, bias = ctx.saved_tensors
         (B, _, H, W), levels, radius = ctx.geom
         want_in = st is not None and ctx.needs_input_grad[0]
@@ -188,18 +190,13 @@ class _LookupConvFn(torch.autograd.Function):
                 return handle_grad, None, None, None, None, None
             corr = None
             if want_w:   # the conv's input again (44 us at DSEC B = 16) instead of 99.5 MB saved per call
-                K = 2 * radius + 1
-                corr = torch.empty((B, levels * K * K, H, W), dtype=torch.float32, device=dev)
+                corr = torch.empty((B, _lib.corr_channels(levels, radius), H, W), dtype=torch.float32, device=dev)
                 _lib.lookup(ctx.pyramid, cc, (B, H, W), H * W, levels, radius, corr, "CorrBlock")
             gi, gw, gb = _lib.conv1x1_relu_backward(go, out, corr, weight, ctx.wcache, want_in, want_w, want_b,
                                                     "CorrBlock lookup+conv1x1+relu backward")
             del corr
             if want_in:
-                if st.G is None:
-                    st.G = torch.zeros(st.numel, dtype=torch.float32, device=dev)
-                _lib.check(_lib.lib().ecorr_lookup_backward(
-                    gi.data_ptr(), cc.data_ptr(), B, H, W, H * W, levels, radius, st.G.data_ptr(),
-                    _lib.stream_of(go)), "CorrBlock lookup backward")
+                st.add_lookup_grad(gi, cc)
         return handle_grad, None, gw, gb, None, None
 
 
@@ -212,17 +209,8 @@ class CorrBlock:
         self.num_levels = num_levels
         self.radius = radius
         self._differentiable = bool(differentiable)   # lookup_conv1x1_relu: weight / bias gradients without live fmaps
-        _require_device_f32("fmap1", fmap1)
-        _require_device_f32("fmap2", fmap2)
         # the gradient path is live only when asked for and needed; otherwise: the plain block
-        live = bool(differentiable) and torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
-        if not live:
-            _no_grad_inputs(fmap1, fmap2)
-        if fmap1.dim() != 4 or fmap1.shape != fmap2.shape:
-            raise RuntimeError(f"fmap shapes {tuple(fmap1.shape)} / {tuple(fmap2.shape)} differ "
-                               "or are not [B, D, H, W]")
-        if fmap1.device != fmap2.device:
-            raise RuntimeError("fmap1 and fmap2 are on different devices")
+        live = _lib.require_fmap_pair(fmap1, fmap2, self._differentiable)
         if not (fmap1.is_contiguous() and fmap2.is_contiguous()):
             # the reference .view()s them (corr.py:55-56), which raises on these strides
             raise RuntimeError("fmap1/fmap2 must be contiguous (reference: view size is not "
@@ -281,22 +269,28 @@ class CorrBlock:
         rounded once to nearest-even: bitwise self(coords).to(out_dtype)); anything else: TypeError."""
         out_dtype = _lib.lookup_out_dtype(out_dtype)
         B, _, H, W = self._shape
-        _require_device_f32("coords", coords)
-        if self._grad is not None and torch.is_grad_enabled() and coords.requires_grad:
+        self._check_coords(coords, train=self._grad is not None)
+        if self._grad is not None:
+            return _LookupFn.apply(self._handle, coords, self._grad, self._pyramid, out_dtype)
+        coords = coords.contiguous()   # the reference accepts any strides (permute + reshape)
+        out = torch.empty((B, _lib.corr_channels(self.num_levels, self.radius), H, W), dtype=out_dtype,
+                          device=self._device)
+        return _lib.lookup(self._pyramid, coords, (B, H, W), H * W, self.num_levels, self.radius, out, "CorrBlock")
+
+    def _check_coords(self, coords, train):
+        """The coords checks of __call__ and lookup_conv1x1_relu; train: the call goes through autograd
+        (then coords that require grad are refused before the shape is looked at)."""
+        B, _, H, W = self._shape
+        require_device("coords", coords)
+        if train and torch.is_grad_enabled() and coords.requires_grad:
             raise RuntimeError("differentiable CorrBlock: coords requires grad; detach it (as eraft.py:127 does), "
                                "there is no gradient with respect to the coordinates")
-        if self._grad is None:
-            _no_grad_inputs(coords)
+        if not train:
+            no_grad_inputs(coords)
         if tuple(coords.shape) != (B, 2, H, W):
             raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
         if coords.device != self._device:
             raise RuntimeError("coords is on a different device than the pyramid")
-        if self._grad is not None:
-            return _LookupFn.apply(self._handle, coords, self._grad, self._pyramid, out_dtype)
-        coords = coords.contiguous()   # the reference accepts any strides (permute + reshape)
-        K = 2 * self.radius + 1
-        out = torch.empty((B, self.num_levels * K * K, H, W), dtype=out_dtype, device=self._device)
-        return _lib.lookup(self._pyramid, coords, (B, H, W), H * W, self.num_levels, self.radius, out, "CorrBlock")
 
     def lookup_conv1x1_relu(self, coords, weight, bias=None, mode=None):
         """F.relu(conv1x1(self(coords), weight, bias)): the lookup followed by
@@ -316,26 +310,21 @@ class CorrBlock:
         A block built with differentiable=True trains through this call (grad mode on, and the block
         live or weight / bias requiring grad): the same launches in the forward (bitwise the plain
         block's values), and in the backward ecorr_conv1x1_relu_backward on the recomputed lookup, then
-        ecorr_lookup_backward into the block's gradient pyramid when the block is live (module
+        the lookup backward into the block's gradient pyramid when the block is live (module
         docstring).  coords that require grad raise, as in corr_fn(coords)."""
         mode = _lib.convc1_mode(mode, presplit=True)
-        B, _, H, W = self._shape
-        _require_device_f32("coords", coords)
         train = self._differentiable and torch.is_grad_enabled() and (
             self._grad is not None or (isinstance(weight, torch.Tensor) and weight.requires_grad)
             or (isinstance(bias, torch.Tensor) and bias.requires_grad))
-        if train and coords.requires_grad:
-            raise RuntimeError("differentiable CorrBlock: coords requires grad; detach it (as eraft.py:127 does), "
-                               "there is no gradient with respect to the coordinates")
-        if not train:
-            _no_grad_inputs(coords)
-        if tuple(coords.shape) != (B, 2, H, W):
-            raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
-        if coords.device != self._device:
-            raise RuntimeError("coords is on a different device than the pyramid")
+        self._check_coords(coords, train)
         if train:
-            _require_device_f32("weight", weight)
+            require_device("weight", weight)
             return _LookupConvFn.apply(self._handle, coords, weight, bias, self, mode)
+        return self._lookup_conv(coords, weight, bias, mode)
+
+    def _lookup_conv(self, coords, weight, bias, mode):
+        """The launches of lookup_conv1x1_relu on checked coords (its plain call and _LookupConvFn.forward)."""
+        B, _, H, W = self._shape
         return _lib.lookup_conv1x1_relu(
             self._pyramid, coords.contiguous(), (B, H, W), H * W, self.num_levels, self.radius, weight, bias, mode,
             lambda O: torch.empty((B, O, H, W), dtype=torch.float32, device=self._device), self._wcache, "CorrBlock",

@@ -9,26 +9,16 @@ One HIP launch each (upsample.hip).  upsample_flow agrees with the reference wit
 (device expf) and is differentiable (two more launches in its backward); the codec is bit-exact.
 No CPU path: inputs must be HIP tensors.
 """
-import ctypes
-
 import torch
 
 from . import _lib
-
-
-def _require_device(name, t, dtype):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.device.type != "cuda":
-        raise RuntimeError(f"{name} is on {t.device}: eraft_amd runs only on HIP devices (no CPU path)")
-    if t.dtype != dtype:
-        raise TypeError(f"{name} must be {dtype} (got {t.dtype})")
+from ._lib import require_device
 
 
 def _upsample(flow, mask):
     """The ecorr_upsample_flow launch on contiguous flow [N, 2, H, W] and mask (N * 576 * H * W elements)."""
     N, _, H, W = flow.shape
-    with torch.cuda.device(flow.device):
+    with _lib.on_device(flow.device):
         out = torch.empty((N, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
         _lib.check(_lib.lib().ecorr_upsample_flow(flow.data_ptr(), mask.data_ptr(), N, H, W, out.data_ptr(),
                                                   _lib.stream_of(flow)), "upsample_flow")
@@ -52,17 +42,14 @@ class _UpsampleFn(torch.autograd.Function):
         go = grad_out.contiguous()   # ImagePadder.unpad: the gradient of a slice
         fc, mc = flow.contiguous(), mask.contiguous()
         need_flow, need_mask = ctx.needs_input_grad
-        with torch.cuda.device(fc.device):
-            nbytes = ctypes.c_int64()
-            _lib.check(_lib.lib().ecorr_upsample_backward_workspace_size(N, H, W, ctypes.byref(nbytes)),
-                       "upsample_flow backward")
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=fc.device)
+        with _lib.on_device(fc.device):
+            ws = _lib.scratch("ecorr_upsample_backward_workspace_size", N, H, W, device=fc.device,
+                              what="upsample_flow backward")
             g_flow = torch.empty((N, 2, H, W), dtype=torch.float32, device=fc.device) if need_flow else None
             g_mask = torch.empty(mask.shape, dtype=torch.float32, device=fc.device) if need_mask else None
             _lib.check(_lib.lib().ecorr_upsample_flow_backward(
-                go.data_ptr(), fc.data_ptr(), mc.data_ptr(), N, H, W,
-                None if g_flow is None else g_flow.data_ptr(), None if g_mask is None else g_mask.data_ptr(),
-                ws.data_ptr(), _lib.stream_of(fc)), "upsample_flow backward")
+                go.data_ptr(), fc.data_ptr(), mc.data_ptr(), N, H, W, _lib.ptr(g_flow), _lib.ptr(g_mask),
+                _lib.ptr(ws), _lib.stream_of(fc)), "upsample_flow backward")
         return g_flow, g_mask
 
 
@@ -70,8 +57,8 @@ def upsample_flow(flow, mask):
     """eraft.py:74-85: flow [N, 2, H, W], mask [N, 576, H, W] -> [N, 2, 8H, 8W].  Differentiable in
     both inputs (ecorr_upsample_flow_backward; deterministic, first order only); with grad mode off, or
     when neither input requires grad, it is the plain launch.  Either way the values are the same bits."""
-    _require_device("flow", flow, torch.float32)
-    _require_device("mask", mask, torch.float32)
+    require_device("flow", flow)
+    require_device("mask", mask)
     if flow.dim() != 4 or flow.shape[1] != 2:
         raise RuntimeError(f"flow must be [N, 2, H, W], got {tuple(flow.shape)}")
     N, _, H, W = flow.shape
@@ -85,14 +72,14 @@ def upsample_flow(flow, mask):
 def flow_to_png16(flow):
     """visualization.py:81-84: flow [2, h, w] (or [B, 2, h, w]) -> uint16 [h, w, 3] ([B, h, w, 3]):
     rint(flow * 128 + 2^15) cast like numpy's astype(uint16), channel 2 = 0."""
-    _require_device("flow", flow, torch.float32)
+    require_device("flow", flow)
     single = flow.dim() == 3
     f = flow.unsqueeze(0) if single else flow
     if f.dim() != 4 or f.shape[1] != 2:
         raise RuntimeError(f"flow must be [2, h, w] or [B, 2, h, w], got {tuple(flow.shape)}")
     f = f.contiguous()
     B, _, h, w = f.shape
-    with torch.cuda.device(f.device):
+    with _lib.on_device(f.device):
         out = torch.empty((B, h, w, 3), dtype=torch.uint16, device=f.device)
         _lib.check(_lib.lib().ecorr_flow_to_png16(f.data_ptr(), B, h, w, out.data_ptr(), _lib.stream_of(f)),
                    "flow_to_png16")
@@ -109,10 +96,10 @@ def flow_16bit_to_float(flow_16bit):
     assert flow_16bit.dim() == 3
     h, w, c = flow_16bit.shape
     assert c == 3
-    _require_device("flow_16bit", flow_16bit, torch.uint16)
+    require_device("flow_16bit", flow_16bit, torch.uint16)
     src = flow_16bit.contiguous()
     dev = src.device
-    with torch.cuda.device(dev):
+    with _lib.on_device(dev):
         flow = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
         valid = torch.empty((h, w), dtype=torch.bool, device=dev)
         bad = torch.zeros((1,), dtype=torch.int32, device=dev)

@@ -24,7 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from ._lib import _no_grad_inputs, _require_device_f32
+from ._lib import no_grad_inputs, require_device
 from .layout import levels_of
 
 
@@ -91,7 +91,7 @@ class RowExchange:
     def gather(self, B, C, W, device):
         """Collective + reassembly of the float32 slabs filled through send_slab: [B, C, H, W]."""
         recv = self.gather_chunks(B, C, W, torch.float32, device)
-        _require_device_f32("rows exchange buffer", recv)
+        require_device("rows exchange buffer", recv)
         out = torch.empty((B, C, self.H, W), dtype=torch.float32, device=recv.device)
         with _lib.on_device(recv.device):
             _lib.check(_lib.lib().ecorr_rows_assemble(
@@ -110,7 +110,7 @@ def gather_rows(slab, counts, group=None):
         raise ValueError(f"row counts {list(counts)} are not the contiguous near-equal partition of {H} rows")
     if world == 1:
         return slab.contiguous()
-    _require_device_f32("slab", slab)
+    require_device("slab", slab)
     B, C, rr, W = slab.shape
     ex = RowExchange(H, group)
     if rr != ex.counts[ex.rank]:
@@ -130,14 +130,7 @@ class RowShardedCorrBlock:
     """
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, group=None):
-        _require_device_f32("fmap1", fmap1)
-        _require_device_f32("fmap2", fmap2)
-        _no_grad_inputs(fmap1, fmap2)
-        if fmap1.dim() != 4 or fmap1.shape != fmap2.shape:
-            raise RuntimeError(f"fmap shapes {tuple(fmap1.shape)} / {tuple(fmap2.shape)} differ "
-                               "or are not [B, D, H, W]")
-        if fmap1.device != fmap2.device:
-            raise RuntimeError("fmap1 and fmap2 are on different devices")
+        _lib.require_fmap_pair(fmap1, fmap2)
         self._ex = RowExchange(fmap1.shape[2], group)
         self.group, self.rank, self.world = group, self._ex.rank, self._ex.world
         self.starts, self.counts = self._ex.starts, self._ex.counts
@@ -147,9 +140,9 @@ class RowShardedCorrBlock:
     @classmethod
     def from_row_slabs(cls, fmap1_rows, fmap2_rows, H, num_levels=4, radius=4, group=None):
         self = cls.__new__(cls)
-        _require_device_f32("fmap1_rows", fmap1_rows)
-        _require_device_f32("fmap2_rows", fmap2_rows)
-        _no_grad_inputs(fmap1_rows, fmap2_rows)
+        require_device("fmap1_rows", fmap1_rows)
+        require_device("fmap2_rows", fmap2_rows)
+        no_grad_inputs(fmap1_rows, fmap2_rows)
         self._ex = RowExchange(H, group)
         self.group, self.rank, self.world = group, self._ex.rank, self._ex.world
         self.starts, self.counts = self._ex.starts, self._ex.counts
@@ -193,8 +186,8 @@ class RowShardedCorrBlock:
     def _local_coords(self, coords_rows):
         B, _, H, W = self._shape
         rr = self.counts[self.rank]
-        _require_device_f32("coords", coords_rows)
-        _no_grad_inputs(coords_rows)
+        require_device("coords", coords_rows)
+        no_grad_inputs(coords_rows)
         if tuple(coords_rows.shape) != (B, 2, rr, W):
             raise RuntimeError(f"coords rows {tuple(coords_rows.shape)} != {(B, 2, rr, W)}")
         if coords_rows.device != self._device:
@@ -210,8 +203,7 @@ class RowShardedCorrBlock:
         """Lookup for this rank's query rows: coords [B, 2, rows_r, W] -> [B, C, rows_r, W]."""
         coords_rows = self._local_coords(coords_rows)
         B, _, H, W = self._shape
-        K = 2 * self.radius + 1
-        C = self.num_levels * K * K
+        C = _lib.corr_channels(self.num_levels, self.radius)
         out = torch.empty((B, C, self.counts[self.rank], W), dtype=torch.float32, device=self._device)
         return self._lookup_into(coords_rows, out)
 
@@ -228,8 +220,7 @@ class RowShardedCorrBlock:
                                       "carries fp32 lookups only; call it without out_dtype and cast the result")
         B, _, H, W = self._shape
         coords_rows = self._full_coords_rows(coords)
-        K = 2 * self.radius + 1
-        C = self.num_levels * K * K
+        C = _lib.corr_channels(self.num_levels, self.radius)
         if self.world == 1:
             out = torch.empty((B, C, H, W), dtype=torch.float32, device=self._device)
             return self._lookup_into(coords_rows, out)

@@ -8,8 +8,6 @@ reference's (single-threaded, main.py:2-5) serial fold and the nonzero normaliza
 an ulp or two (voxel.hip).  No CPU path: the DSEC events must be fp32 HIP tensors; the MVSEC
 sequence's float64 features are copied to the HIP device like the reference's gpu=True mode.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -17,10 +15,8 @@ from . import _lib
 
 
 def _workspace(dsec, n, C, H, W, device):
-    nbytes = ctypes.c_int64()
-    _lib.check(_lib.lib().ecorr_voxel_workspace_size(int(dsec), n, C, H, W, ctypes.byref(nbytes)),
-               "voxel workspace")
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
+    return _lib.scratch("ecorr_voxel_workspace_size", int(dsec), n, C, H, W, device=device, what="voxel workspace",
+                        min_bytes=1)
 
 
 class VoxelGrid:
@@ -44,7 +40,7 @@ class VoxelGrid:
             raise IndexError("index 0 is out of bounds for dimension 0 with size 0")
         p, t, x, y = (v.reshape(-1).contiguous() for v in ts)
         dev = p.device
-        with torch.no_grad(), torch.cuda.device(dev):
+        with torch.no_grad(), _lib.on_device(dev):
             voxel = torch.empty((C, H, W), dtype=torch.float32, device=dev)
             ws = _workspace(True, n, C, H, W, dev)
             _lib.check(_lib.lib().ecorr_voxel_grid_dsec(
@@ -77,7 +73,7 @@ class EventSequenceToVoxelGrid_Pytorch:
         n = ev.shape[0]
         if n == 0:
             raise IndexError("index -1 is out of bounds for dimension 0 with size 0")
-        with torch.no_grad(), torch.cuda.device(self.device):
+        with torch.no_grad(), _lib.on_device(self.device):
             voxel = torch.empty((self.num_bins, height, width), dtype=torch.float32, device=self.device)
             bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
             ws = _workspace(False, n, self.num_bins, height, width, self.device)
