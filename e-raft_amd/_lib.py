@@ -32,6 +32,9 @@ ECORR_OUT_F32 = 0
 ECORR_OUT_F16 = 1
 ECORR_OUT_BF16 = 2
 OUT_FORMATS = {torch.float32: ECORR_OUT_F32, torch.float16: ECORR_OUT_F16, torch.bfloat16: ECORR_OUT_BF16}
+# the same codes as an input format (ECORR_ELEM_*: ecorr_build_split_pack_as's fmap_format)
+ECORR_ELEM_F32, ECORR_ELEM_F16, ECORR_ELEM_BF16 = ECORR_OUT_F32, ECORR_OUT_F16, ECORR_OUT_BF16
+ELEM_FORMATS = OUT_FORMATS
 
 _lib = None
 
@@ -53,6 +56,11 @@ SYMBOLS = {
     "ecorr_build_split": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (fmap1, fmap2, B, D, H, W, q_count, workspace, stream)
     "ecorr_build_split_pack": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    # 16-bit (or fp32) fmaps in (added within ABI 17):
+    # (fmap1, fmap2, fmap_format, B, D, H, W, q_count, workspace, stream) /
+    # (fmap1, fmap2, fmap_format, B, D, H, W, q_count, levels, pyramid, workspace, stream)
+    "ecorr_build_split_pack_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "ecorr_build_split_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (B, D, H, W, q_count, levels, pyramid, workspace, stream)
     "ecorr_build_split_gemm": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (pyramid, coords, B, H, W, q_count, levels, radius, out, stream)
@@ -70,11 +78,15 @@ SYMBOLS = {
     "ecorr_conv1x1_packed_size": (_i, [_i, _i, ctypes.POINTER(_i64)]),
     "ecorr_conv1x1_pack": (_i, [_p, _i, _i, _p, _p]),
     "ecorr_lookup_conv1x1_relu_packed": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
+    # a 16-bit (or fp32) convc1 output (added within ABI 17): as the packed entry, out_format before out
+    "ecorr_lookup_conv1x1_relu_packed_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p]),
     # (O, C, bytes*) / (weight[O][C], O, C, packed, stream) /
     # (in[B][C][Q], B, C, Q, qmax, G, packed, bias, O, out, stream): split-f16 convc1 + ReLU (ABI 15)
     "ecorr_conv1x1_split_size": (_i, [_i, _i, ctypes.POINTER(_i64)]),
     "ecorr_conv1x1_split_pack": (_i, [_p, _i, _i, _p, _p]),
     "ecorr_conv1x1_relu_split": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p]),
+    # (in[B][C][Q], B, C, Q, qmax, G, packed, bias, O, out_format, out, stream) (added within ABI 17)
+    "ecorr_conv1x1_relu_split_as": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _i, _i, _p, _p]),
     # its backward (added within ABI 17): (B, C, Q, O, bytes*) /
     # (grad_out, out, in, packed_t, B, C, Q, O, grad_in, grad_weight, grad_bias, workspace, stream)
     "ecorr_conv1x1_relu_backward_workspace_size": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i64)]),
@@ -186,11 +198,20 @@ def no_grad_inputs(*ts):
                            "(as the reference harness does, test.py:80)")
 
 
-def require_fmap_pair(fmap1, fmap2, differentiable=False):
-    """The fmap checks of CorrBlock and RowShardedCorrBlock.  Returns whether the gradient path is live:
-    asked for (differentiable) and needed; otherwise fmaps that require grad raise."""
-    require_device("fmap1", fmap1)
-    require_device("fmap2", fmap2)
+def fmap_dtype_of(fmap_dtype):
+    """The dtype both fmaps must have for the fmap_dtype argument of CorrBlock: None = float32."""
+    if fmap_dtype is None:
+        return torch.float32
+    if fmap_dtype not in ELEM_FORMATS:
+        raise TypeError(f"fmap_dtype must be None, torch.float32, torch.float16 or torch.bfloat16 (got {fmap_dtype!r})")
+    return fmap_dtype
+
+
+def require_fmap_pair(fmap1, fmap2, differentiable=False, dtype=torch.float32):
+    """The fmap checks of CorrBlock and RowShardedCorrBlock (both fmaps of `dtype`).  Returns whether the
+    gradient path is live: asked for (differentiable) and needed; otherwise fmaps that require grad raise."""
+    require_device("fmap1", fmap1, dtype)
+    require_device("fmap2", fmap2, dtype)
     live = differentiable and torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
     if not live:
         no_grad_inputs(fmap1, fmap2)
@@ -296,7 +317,10 @@ def build_mode() -> str:
 def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=None):
     """Allocate the pyramid (levels at off[i]) on fmap2's device and build it on the current
     stream.  The split build's workspace (exponents + packed f16 operand panels, about the fmaps'
-    size) is a temporary from the caching allocator, released stream-ordered after the launch."""
+    size) is a temporary from the caching allocator, released stream-ordered after the launch.
+    float16 / bfloat16 fmaps (both of one dtype, checked by the caller): the split build's operand pass
+    reads them as they are (ecorr_build_split_pack_as: bitwise the pack of their .float()); the fp32
+    build has no 16-bit input and gets .float() temporaries."""
     mode = mode or _build_mode
     if mode not in BUILD_MODES:
         raise ValueError(f"build mode {mode!r} not in {BUILD_MODES}")
@@ -310,8 +334,12 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
             ev = [mk() if stage_event_start else None, mk(), mk()]
             if ev[0] is not None:
                 ev[0].record()
-        check(lib().ecorr_build_split_pack(fmap1.data_ptr(), fmap2.data_ptr(), B, D, H, W, q_count,
-                                           ws.data_ptr(), st), what)
+        if fmap1.dtype == torch.float32:
+            check(lib().ecorr_build_split_pack(fmap1.data_ptr(), fmap2.data_ptr(), B, D, H, W, q_count,
+                                               ws.data_ptr(), st), what)
+        else:
+            check(lib().ecorr_build_split_pack_as(fmap1.data_ptr(), fmap2.data_ptr(), ELEM_FORMATS[fmap1.dtype],
+                                                  B, D, H, W, q_count, ws.data_ptr(), st), what)
         if tm is not None:
             ev[1].record()
         check(lib().ecorr_build_split_gemm(B, D, H, W, q_count, levels, pyr.data_ptr(), ws.data_ptr(), st),
@@ -321,7 +349,8 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
             tm.append(ev)
         del ws
     else:
-        check(lib().ecorr_build(fmap1.data_ptr(), fmap2.data_ptr(), B, D, H, W, q_count, levels,
+        f1, f2 = fmap1.float(), fmap2.float()   # (fp32 fmaps: themselves)
+        check(lib().ecorr_build(f1.data_ptr(), f2.data_ptr(), B, D, H, W, q_count, levels,
                                 pyr.data_ptr(), st), what)
     return pyr
 
@@ -405,7 +434,9 @@ def lookup_conv1x1_relu(pyramid, coords, shape, q_count, levels, radius, weight,
     """relu(conv1x1(lookup(coords), weight, bias)) for the q_count queries of one block (CorrBlock: all
     H * W; RowShardedCorrBlock: its rows): the body of both classes' lookup_conv1x1_relu.
     coords: contiguous [B][2][q_count], checked by the caller; shape = (B, H, W) of the build;
-    alloc_out(O) -> the fp32 tensor of B * O * q_count elements to write (returned); cache: the
+    alloc_out(O) -> the tensor of B * O * q_count elements to write (returned): fp32, or float16 /
+    bfloat16 for the 16-bit output (the *_as entries of modes "split" and "fused"; "presplit" has no
+    16-bit form and then runs as "split"); cache: the
     block's packed-weight cache; what: the class name for error texts.
     mode: what convc1_mode returned (the callers resolve it before their coords checks).
     column_scale (mode "presplit"): stream -> the presplit column exponents, or None when the block
@@ -431,6 +462,9 @@ def lookup_conv1x1_relu(pyramid, coords, shape, q_count, levels, radius, weight,
     with on_device(dev):
         out = alloc_out(O)
         st = stream_of(out)
+        fmt = OUT_FORMATS[out.dtype]
+        if mode == "presplit" and fmt != ECORR_OUT_F32:
+            mode = "split"
         if mode == "presplit":
             scale = column_scale(st) if radius == 4 and levels <= 4 else None
             if scale is None:
@@ -451,12 +485,21 @@ def lookup_conv1x1_relu(pyramid, coords, shape, q_count, levels, radius, weight,
             check(lib().ecorr_lookup_qmax(
                 pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, corr.data_ptr(),
                 qmax.data_ptr(), st), f"{what} lookup (split convc1)")
-            check(lib().ecorr_conv1x1_relu_split(
-                corr.data_ptr(), B, C, q_count, qmax.data_ptr(), G, wt.data_ptr(), bptr, O, out.data_ptr(), st),
-                f"{what} lookup+conv1x1+relu (split)")
-        else:
+            if fmt == ECORR_OUT_F32:
+                check(lib().ecorr_conv1x1_relu_split(
+                    corr.data_ptr(), B, C, q_count, qmax.data_ptr(), G, wt.data_ptr(), bptr, O, out.data_ptr(), st),
+                    f"{what} lookup+conv1x1+relu (split)")
+            else:
+                check(lib().ecorr_conv1x1_relu_split_as(
+                    corr.data_ptr(), B, C, q_count, qmax.data_ptr(), G, wt.data_ptr(), bptr, O, fmt, out.data_ptr(),
+                    st), f"{what} lookup+conv1x1+relu (split)")
+        elif fmt == ECORR_OUT_F32:
             check(lib().ecorr_lookup_conv1x1_relu_packed(
                 pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, wt.data_ptr(), bptr, O,
+                out.data_ptr(), st), f"{what} lookup+conv1x1+relu")
+        else:
+            check(lib().ecorr_lookup_conv1x1_relu_packed_as(
+                pyramid.data_ptr(), coords.data_ptr(), B, H, W, q_count, levels, radius, wt.data_ptr(), bptr, O, fmt,
                 out.data_ptr(), st), f"{what} lookup+conv1x1+relu")
     return out
 

@@ -23,7 +23,23 @@ rounded once to nearest-even, bitwise `corr_fn(coords).to(dtype)`, stored by the
 -- half the output bytes and no cast kernel in front of an autocast convc1 (eraft.py:131-132).
 out_dtype None or torch.float32 is the fp32 call exactly; any other dtype raises TypeError.  On a
 differentiable block the 16-bit lookup is differentiable too: its backward converts the incoming
-gradient with .float() and runs the fp32 backward.  lookup_conv1x1_relu keeps its fp32 output.
+gradient with .float() and runs the fp32 backward.
+
+16-bit at both ends: `CorrBlock(f1, f2, ..., fmap_dtype=torch.float16 | torch.bfloat16)`
+takes both fmaps in that dtype, as fnet returns them under autocast, and the split build's operand pass
+reads them itself (ecorr_build_split_pack_as): the 16-bit -> fp32 conversion is exact, so the pyramid is
+bitwise that of `CorrBlock(f1.float(), f2.float(), ...)` with two cast kernels and half the pack's read
+bytes less.  fmap_dtype None / torch.float32 is the fp32 check and path exactly (a 16-bit fmap without
+the keyword still raises); another dtype, or fmaps of different dtypes, raise TypeError.  With
+ECORR_BUILD_MODE=fp32 (no 16-bit input there) the block converts with .float() and builds as before.
+The presplit convc1 mode needs fp32 fmaps for its column scale, so on a 16-bit block it takes its
+documented fallback, "split".  A differentiable block saves the 16-bit fmaps; its backward converts
+them with .float() as temporaries, runs ecorr_build_backward and returns the gradients cast to the
+fmaps' dtype -- what autograd's own .float() node would hand back, so fmap.grad is bitwise that of the
+fp32 block on fmap.float().
+`corr_fn.lookup_conv1x1_relu(coords, weight, bias, out_dtype=...)` returns relu(convc1(corr)) in that
+dtype from the conv's own epilogue (ecorr_conv1x1_relu_split_as / ecorr_lookup_conv1x1_relu_packed_as):
+bitwise the fp32 call's result cast once, with no cast kernel in front of an autocast convc2.
 
 Training (opt-in): CorrBlock(fmap1, fmap2, num_levels, radius, differentiable=True) accepts fmaps
 that require grad and gives them gradients through the build and every `corr_fn(coords)` lookup
@@ -105,7 +121,7 @@ class _BuildFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fmap1, fmap2, state):
         ctx.state = state
-        ctx.save_for_backward(fmap1, fmap2)
+        ctx.save_for_backward(fmap1, fmap2)   # as given: 16-bit fmaps (fmap_dtype) are saved as 16-bit
         return torch.zeros(1, dtype=torch.float32, device=state.device)
 
     @staticmethod
@@ -118,14 +134,21 @@ class _BuildFn(torch.autograd.Function):
         B, D, H, W = st.shape
         n1, n2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         G, st.G = st.G, None
+        dt = f1.dtype
         with _lib.on_device(st.device):
-            g1 = torch.empty_like(f1) if n1 else None
-            g2 = torch.empty_like(f2) if n2 else None
             if G is None:   # no lookup received a gradient
-                return (None if g1 is None else g1.zero_(), None if g2 is None else g2.zero_(), None)
+                return (torch.zeros_like(f1) if n1 else None, torch.zeros_like(f2) if n2 else None, None)
+            # the backward is fp32: 16-bit fmaps as fp32 temporaries (exact), the gradients cast to the
+            # fmaps' dtype as autograd's own .float() node would hand them back
+            g1 = torch.empty(f1.shape, dtype=torch.float32, device=st.device) if n1 else None
+            g2 = torch.empty(f2.shape, dtype=torch.float32, device=st.device) if n2 else None
+            f1, f2 = f1.float(), f2.float()
             _lib.check(_lib.lib().ecorr_build_backward(
                 G.data_ptr(), f1.data_ptr(), f2.data_ptr(), B, D, H, W, H * W, st.levels,
                 _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(f1)), "CorrBlock build backward")
+            if dt != torch.float32:
+                g1 = None if g1 is None else g1.to(dt)
+                g2 = None if g2 is None else g2.to(dt)
         return g1, g2, None
 
 
@@ -161,8 +184,8 @@ class _LookupConvFn(torch.autograd.Function):
     backward recomputes it (ecorr_lookup) when the weight needs its gradient."""
 
     @staticmethod
-    def forward(ctx, handle, coords, weight, bias, blk, mode):
-        out = blk._lookup_conv(coords, weight, bias, mode)
+    def forward(ctx, handle, coords, weight, bias, blk, mode, out_dtype=torch.float32):
+        out = blk._lookup_conv(coords, weight, bias, mode, out_dtype)
         # what the backward reads of the block, not the block: the pyramid, the geometry, the shared
         # gradient state (None: not live) and the packed-weight cache
         ctx.pyramid, ctx.state, ctx.wcache = blk._pyramid, blk._grad, blk._wcache
@@ -182,12 +205,15 @@ class _LookupConvFn(torch.autograd.Function):
         want_w = ctx.needs_input_grad[2]
         want_b = bias is not None and ctx.needs_input_grad[3]
         dev = out.device
-        go = grad_out.contiguous()
         cc = coords.contiguous()
         with _lib.on_device(dev):
             handle_grad = None if st is None else torch.zeros(1, dtype=torch.float32, device=dev)
             if not (want_in or want_w or want_b):
-                return handle_grad, None, None, None, None, None
+                return handle_grad, None, None, None, None, None, None
+            # a 16-bit output: the fp32 backward on its exact values -- the ReLU mask is the saved 16-bit
+            # output's, as autocast's own ReLU would take it
+            go = grad_out.float().contiguous()
+            out = out.float()
             corr = None
             if want_w:   # the conv's input again (44 us at DSEC B = 16) instead of 99.5 MB saved per call
                 corr = torch.empty((B, _lib.corr_channels(levels, radius), H, W), dtype=torch.float32, device=dev)
@@ -197,20 +223,23 @@ class _LookupConvFn(torch.autograd.Function):
             del corr
             if want_in:
                 st.add_lookup_grad(gi, cc)
-        return handle_grad, None, gw, gb, None, None
+        return handle_grad, None, gw, gb, None, None, None
 
 
 class CorrBlock:
     """All-pairs correlation pyramid + radius-r lookup (reference: model/corr.py:12-60).
     differentiable=True (keyword only): gradients for fmap1 / fmap2, and through
-    lookup_conv1x1_relu for its weight and bias too (module docstring)."""
+    lookup_conv1x1_relu for its weight and bias too (module docstring).
+    fmap_dtype (keyword only): None / torch.float32 = fp32 fmaps (the reference's); torch.float16 /
+    torch.bfloat16 = both fmaps in that dtype, read by the split build as they are (module docstring)."""
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, differentiable=False):
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, differentiable=False, fmap_dtype=None):
         self.num_levels = num_levels
         self.radius = radius
         self._differentiable = bool(differentiable)   # lookup_conv1x1_relu: weight / bias gradients without live fmaps
         # the gradient path is live only when asked for and needed; otherwise: the plain block
-        live = _lib.require_fmap_pair(fmap1, fmap2, self._differentiable)
+        self._fmap_dtype = _lib.fmap_dtype_of(fmap_dtype)
+        live = _lib.require_fmap_pair(fmap1, fmap2, self._differentiable, self._fmap_dtype)
         if not (fmap1.is_contiguous() and fmap2.is_contiguous()):
             # the reference .view()s them (corr.py:55-56), which raises on these strides
             raise RuntimeError("fmap1/fmap2 must be contiguous (reference: view size is not "
@@ -292,11 +321,15 @@ class CorrBlock:
         if coords.device != self._device:
             raise RuntimeError("coords is on a different device than the pyramid")
 
-    def lookup_conv1x1_relu(self, coords, weight, bias=None, mode=None):
+    def lookup_conv1x1_relu(self, coords, weight, bias=None, mode=None, out_dtype=None):
         """F.relu(conv1x1(self(coords), weight, bias)): the lookup followed by
         BasicMotionEncoder.convc1 + ReLU (update.py:67,74).
         weight: [O, C, 1, 1] (or [O, C]) fp32 with C = num_levels * (2r+1)^2; bias: [O] or None.
-        Returns [B, O, H, W].  mode (default: env ECORR_CONVC1, else "split"):
+        Returns [B, O, H, W] in out_dtype: None / torch.float32, or torch.float16 / torch.bfloat16 -- each
+        element the fp32 call's value (after bias and ReLU) rounded once to nearest-even by the conv's own
+        epilogue, bitwise self.lookup_conv1x1_relu(...).to(out_dtype), in modes "split" and "fused"
+        ("presplit" with a 16-bit out_dtype runs as "split"); weight and bias stay fp32; anything else:
+        TypeError.  mode (default: env ECORR_CONVC1, else "split"):
           "split"  ecorr_lookup_qmax into a temporary [B, C, H, W] (+ per-query maxima), then
                    ecorr_conv1x1_relu_split (f16 matrix cores, split operands: normwise within 1e-5
                    of the fp32 conv);
@@ -311,28 +344,36 @@ class CorrBlock:
         live or weight / bias requiring grad): the same launches in the forward (bitwise the plain
         block's values), and in the backward ecorr_conv1x1_relu_backward on the recomputed lookup, then
         the lookup backward into the block's gradient pyramid when the block is live (module
-        docstring).  coords that require grad raise, as in corr_fn(coords)."""
+        docstring).  coords that require grad raise, as in corr_fn(coords).  With a 16-bit
+        out_dtype the saved output is the 16-bit one and the backward runs the fp32 backward on
+        out.float() and grad_out.float(): the ReLU mask is taken from the 16-bit output, as autocast's own
+        ReLU would take it, so the gradients differ from the fp32-output call's only where a positive
+        fp32 output rounds to 0 in 16 bits."""
         mode = _lib.convc1_mode(mode, presplit=True)
+        out_dtype = _lib.lookup_out_dtype(out_dtype)
         train = self._differentiable and torch.is_grad_enabled() and (
             self._grad is not None or (isinstance(weight, torch.Tensor) and weight.requires_grad)
             or (isinstance(bias, torch.Tensor) and bias.requires_grad))
         self._check_coords(coords, train)
         if train:
             require_device("weight", weight)
-            return _LookupConvFn.apply(self._handle, coords, weight, bias, self, mode)
-        return self._lookup_conv(coords, weight, bias, mode)
+            return _LookupConvFn.apply(self._handle, coords, weight, bias, self, mode, out_dtype)
+        return self._lookup_conv(coords, weight, bias, mode, out_dtype)
 
-    def _lookup_conv(self, coords, weight, bias, mode):
+    def _lookup_conv(self, coords, weight, bias, mode, out_dtype=torch.float32):
         """The launches of lookup_conv1x1_relu on checked coords (its plain call and _LookupConvFn.forward)."""
         B, _, H, W = self._shape
         return _lib.lookup_conv1x1_relu(
             self._pyramid, coords.contiguous(), (B, H, W), H * W, self.num_levels, self.radius, weight, bias, mode,
-            lambda O: torch.empty((B, O, H, W), dtype=torch.float32, device=self._device), self._wcache, "CorrBlock",
+            lambda O: torch.empty((B, O, H, W), dtype=out_dtype, device=self._device), self._wcache, "CorrBlock",
             column_scale=self._column_scale)
 
     def _column_scale(self, st):
         """int[B*H*W + B]: the presplit column exponents (ecorr_split_column_scale), once per block;
-        None when the fmaps are gone or were changed in place since the build."""
+        None when the fmaps are gone or were changed in place since the build, or are 16-bit (the
+        scale kernel reads fp32)."""
+        if self._fmap_dtype != torch.float32:
+            return None
         if self._colscale is None:
             r1, r2, v1, v2 = self._fmap_refs
             f1, f2 = r1(), r2()

@@ -107,8 +107,9 @@ ECORR_EXPORT int ecorr_pyramid_formats(int H, int W, int levels, int* ntx) {
 
 namespace {
 
+// fmap_format (split build): ECORR_ELEM_* of the elements fmap1 / fmap2 point at
 int build_common(const float* fmap1, const float* fmap2, int B, int D, int H, int W, int q_count, int levels,
-                 float* pyramid, void* workspace, void* stream, int stages = 3) {
+                 float* pyramid, void* workspace, void* stream, int stages = 3, int fmap_format = ECORR_ELEM_F32) {
     if ((stages & 1) && (!fmap1 || !fmap2)) return ECORR_EINVAL;
     if ((stages & 2) && !pyramid) return ECORR_EINVAL;
     if (B <= 0 || D <= 0) return ECORR_EINVAL;
@@ -136,7 +137,7 @@ int build_common(const float* fmap1, const float* fmap2, int B, int D, int H, in
         if (B > 65535 || ((uintptr_t)workspace & 255)) return ECORR_EINVAL;
         P.ws = static_cast<char*>(workspace);
     }
-    return launch_build(P, B, g, pyramid, (hipStream_t)stream, stages);
+    return launch_build(P, B, g, pyramid, (hipStream_t)stream, stages, fmap_format);
 }
 
 }  // namespace
@@ -162,6 +163,20 @@ ECORR_EXPORT int ecorr_build_split_pack(const float* fmap1, const float* fmap2, 
                                         int q_count, void* workspace, void* stream) {
     if (!workspace) return ECORR_EINVAL;
     return build_common(fmap1, fmap2, B, D, H, W, q_count, 1, nullptr, workspace, stream, 1);
+}
+
+ECORR_EXPORT int ecorr_build_split_pack_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H,
+                                           int W, int q_count, void* workspace, void* stream) {
+    if (!workspace) return ECORR_EINVAL;
+    return build_common((const float*)fmap1, (const float*)fmap2, B, D, H, W, q_count, 1, nullptr, workspace, stream, 1,
+                        fmap_format);
+}
+
+ECORR_EXPORT int ecorr_build_split_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
+                                      int q_count, int levels, float* pyramid, void* workspace, void* stream) {
+    if (!workspace) return ECORR_EINVAL;
+    return build_common((const float*)fmap1, (const float*)fmap2, B, D, H, W, q_count, levels, pyramid, workspace,
+                        stream, 3, fmap_format);
 }
 
 ECORR_EXPORT int ecorr_build_split_gemm(int B, int D, int H, int W, int q_count, int levels, float* pyramid,
@@ -312,6 +327,17 @@ ECORR_EXPORT int ecorr_lookup_conv1x1_relu_packed(const float* pyramid, const fl
     return launch_lookup_conv(P, B, packed, bias, O, out, (hipStream_t)stream, true);
 }
 
+ECORR_EXPORT int ecorr_lookup_conv1x1_relu_packed_as(const float* pyramid, const float* coords, int B, int H, int W,
+                                                     int q_count, int levels, int radius, const float* packed,
+                                                     const float* bias, int O, int out_format, void* out,
+                                                     void* stream) {
+    if (!packed) return ECORR_EINVAL;
+    LookupParams P{};
+    const int st = lookup_params(pyramid, coords, B, H, W, q_count, levels, radius, (float*)out, &P);
+    if (st != ECORR_OK) return st;
+    return launch_lookup_conv(P, B, packed, bias, O, (float*)out, (hipStream_t)stream, true, out_format);
+}
+
 ECORR_EXPORT int ecorr_conv1x1_split_size(int O, int C, int64_t* bytes) {
     if (!bytes || O <= 0 || C <= 0) return ECORR_EINVAL;
     *bytes = conv1x1_split_bytes(O, C);
@@ -327,6 +353,14 @@ ECORR_EXPORT int ecorr_conv1x1_relu_split(const float* in, int B, int C, int Q, 
                                           const void* packed, const float* bias, int O, float* out, void* stream) {
     if (!in || !packed || !out) return ECORR_EINVAL;
     return launch_conv1x1_relu_split(in, B, C, Q, qmax, G, packed, bias, O, out, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_conv1x1_relu_split_as(const float* in, int B, int C, int Q, const float* qmax, int G,
+                                             const void* packed, const float* bias, int O, int out_format, void* out,
+                                             void* stream) {
+    if (!in || !packed || !out) return ECORR_EINVAL;
+    return launch_conv1x1_relu_split(in, B, C, Q, qmax, G, packed, bias, O, (float*)out, (hipStream_t)stream,
+                                     out_format);
 }
 
 ECORR_EXPORT int ecorr_conv1x1_relu_backward_workspace_size(int B, int C, int Q, int O, int64_t* bytes) {

@@ -25,6 +25,7 @@
 // §3.1 keeps the record); lab builds for new A/Bs are separate .so files (tools/).
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "out_elem.h"
 #include "split_f16.h"
 
 #include <type_traits>
@@ -1238,8 +1239,17 @@ __global__ __launch_bounds__(256, 2) void build_f32_kernel(BuildParams P) {
 // L16: the panel layout of build_split16_kernel (16 KB per 128-pixel tile and 32-deep chunk pair:
 // [16-pixel group g][hi | lo][k block kb][pixel r][8 halves], k = 8 kb + j within the pair; fmap2
 // positions in split16_target order) instead of build_split_kernel's 8-KB chunk panels.
-template <bool ISB, bool L16>
-__device__ __forceinline__ void pack_body(const float* __restrict__ x, const BuildParams& P, int* __restrict__ ex,
+//
+// T: the element the operands are stored as (float, _Float16 or __bf16: ecorr_build_split_pack_as),
+// converted to fp32 on load -- exactly; everything after the load is the fp32 pass.  Lanes stay
+// consecutive pixels (2-byte loads: a 16-bit slab view may be 2-byte aligned only).  A 16-bit element
+// is loaded as its bit pattern (0 where the lane has no pixel or k >= D); on the register path all
+// of a thread's patterns are loaded before the first is converted: with the convert beside the load
+// hipcc keeps it inside the load's branch with a vmcnt(0) wait behind it -- 64 serialized round
+// trips per thread where the fp32 pass has its loads in flight together (the pack alone 98 vs 63 us
+// at DSEC B = 16 in that form, profiles/half_io/).
+template <bool ISB, bool L16, typename T>
+__device__ __forceinline__ void pack_body(const T* __restrict__ x, const BuildParams& P, int* __restrict__ ex,
                                           char* __restrict__ pack) {
     __shared__ float red[4][64];
     const int b = blockIdx.y;
@@ -1283,24 +1293,51 @@ __device__ __forceinline__ void pack_body(const float* __restrict__ x, const Bui
         live = ok;
         if (ok && n.ty0 + y < P.H && n.tx0 + x < P.W) pix = (int64_t)(n.ty0 + y) * P.W + n.tx0 + x;
     }
-    const float* px = x + (int64_t)b * D * N + (pix < 0 ? 0 : pix);
+    using Raw = std::conditional_t<std::is_same_v<T, float>, float, unsigned short>;   // the element as loaded
+    const Raw* px = reinterpret_cast<const Raw*>(x) + (int64_t)b * D * N + (pix < 0 ? 0 : pix);
+    auto cv = [](Raw r) -> float {
+        if constexpr (std::is_same_v<T, float>) return r;
+        else return (float)__builtin_bit_cast(T, r);
+    };
     constexpr int CPT = 4;
     const bool regs = dc <= 4 * CPT;
     float v[CPT][16];
     float m = 0.f;
     if (regs) {
+        if constexpr (std::is_same_v<T, float>) {
 #pragma unroll
-        for (int i = 0; i < CPT; ++i)
+            for (int i = 0; i < CPT; ++i)
 #pragma unroll
-            for (int kk = 0; kk < 16; ++kk) {
-                const int k = (qtr + 4 * i) * 16 + kk;
-                v[i][kk] = (pix >= 0 && k < D) ? px[(int64_t)k * N] : 0.f;
-                m = fmaxf(m, fabsf(v[i][kk]));
-            }
+                for (int kk = 0; kk < 16; ++kk) {
+                    const int k = (qtr + 4 * i) * 16 + kk;
+                    v[i][kk] = (pix >= 0 && k < D) ? px[(int64_t)k * N] : 0.f;
+                    m = fmaxf(m, fabsf(v[i][kk]));
+                }
+        } else {
+            // all the bit patterns first, each pinned in its register behind the last load, then the
+            // converts: left to itself hipcc converts inside each load's branch, with a vmcnt(0)
+            // wait per load (see above)
+            unsigned r[CPT][16];
+#pragma unroll
+            for (int i = 0; i < CPT; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 16; ++kk) {
+                    const int k = (qtr + 4 * i) * 16 + kk;
+                    r[i][kk] = (pix >= 0 && k < D) ? px[(int64_t)k * N] : 0u;
+                }
+#pragma unroll
+            for (int i = 0; i < CPT; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 16; ++kk) {
+                    asm volatile("" : "+v"(r[i][kk]));
+                    v[i][kk] = cv((Raw)r[i][kk]);
+                    m = fmaxf(m, fabsf(v[i][kk]));
+                }
+        }
     } else if (pix >= 0) {
         for (int k = qtr * 16; k < D; k += 64)
 #pragma unroll 4
-            for (int kk = 0; kk < 16 && k + kk < D; ++kk) m = fmaxf(m, fabsf(px[(int64_t)(k + kk) * N]));
+            for (int kk = 0; kk < 16 && k + kk < D; ++kk) m = fmaxf(m, fabsf(cv(px[(int64_t)(k + kk) * N])));
     }
     red[qtr][threadIdx.x & 63] = m;
     __syncthreads();
@@ -1336,9 +1373,8 @@ __device__ __forceinline__ void pack_body(const float* __restrict__ x, const Bui
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             const int k = c * 16 + kk;
-            w[kk] = (pix >= 0 && k < D) ? px[(int64_t)k * N] : 0.f;
-        }
-        put(c, w);
+            w[kk] = cv((pix >= 0 && k < D) ? px[(int64_t)k * N] : Raw(0));
+        }        put(c, w);
     }
 }
 
@@ -1346,12 +1382,14 @@ __device__ __forceinline__ void pack_body(const float* __restrict__ x, const Bui
 // tiles), z = 1 fmap2 (n-tiles).  Neither pass alone fills the chip; one grid overlaps the two and
 // drops a launch boundary (round-1 A/B, profiles/r01_final8/ab_pack.txt).  Surplus x blocks of the
 // shorter pass return at once (block-uniform, before pack_body's barrier).
-template <bool L16>
+// T: the fmaps' element (P.f1 / P.f2 point at elements of T; float: the fp32 entries).
+template <bool L16, typename T = float>
 __global__ __launch_bounds__(256) void pack_both_kernel(BuildParams P) {
     if (blockIdx.z == 0) {
-        if ((int)blockIdx.x < 2 * P.n_mt) pack_body<false, L16>(P.f1, P, P.ex1, const_cast<char*>(P.pk1));
+        if ((int)blockIdx.x < 2 * P.n_mt)
+            pack_body<false, L16, T>(reinterpret_cast<const T*>(P.f1), P, P.ex1, const_cast<char*>(P.pk1));
     } else if ((int)blockIdx.x < 4 * (P.n_reg / P.n_ntx) * ((P.n_ntx + 1) / 2) + 2 * (P.n_nt - P.n_reg)) {
-        pack_body<true, L16>(P.f2, P, P.ex2, const_cast<char*>(P.pk2));
+        pack_body<true, L16, T>(reinterpret_cast<const T*>(P.f2), P, P.ex2, const_cast<char*>(P.pk2));
     }
 }
 
@@ -1799,7 +1837,17 @@ int64_t build_split_workspace_bytes(int B, int D, int H, int W, int q_count) {
     return split_ws(P, B).total;
 }
 
-int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid, hipStream_t stream, int stages) {
+namespace {
+// the operand pass on fmaps of element T (ECORR_ELEM_*: InElem)
+template <typename T>
+void launch_pack(const BuildParams& P, int nx, int B, bool s16, hipStream_t stream) {
+    if (s16) hipLaunchKernelGGL((pack_both_kernel<true, T>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL((pack_both_kernel<false, T>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
+}
+}  // namespace
+
+int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid, hipStream_t stream, int stages,
+                 int fmap_format) {
     BuildParams P = P0;
     const int levels = g.levels;
     P.fused_levels = levels < 4 ? levels : 4;
@@ -1812,6 +1860,9 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
         const int64_t ntiles = (int64_t)B * P.n_qt * P.n_nt;
         if (ntiles <= 0 || ntiles > 0x7fffffff || (int64_t)2 * ((P.D + 15) / 16) * PANEL >= 0x7fff0000LL)
             return ECORR_EINVAL;
+        if ((stages & 1) && fmap_format != ECORR_ELEM_F32 && fmap_format != ECORR_ELEM_F16 &&
+            fmap_format != ECORR_ELEM_BF16)
+            return ECORR_EINVAL;
         const SplitWs w = split_ws(P, B);
         P.ex1 = reinterpret_cast<int*>(P.ws);
         P.ex2 = reinterpret_cast<int*>(P.ws + w.ex2);
@@ -1822,8 +1873,9 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
         // D = 256: build_split16_kernel and its panel layout; other D: build_split_kernel
         const bool s16 = (P.D + 15) / 16 == 2 * NCP;
         if (stages & 1) {
-            if (s16) hipLaunchKernelGGL((pack_both_kernel<true>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
-            else hipLaunchKernelGGL((pack_both_kernel<false>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
+            if (fmap_format == ECORR_ELEM_F16) launch_pack<InElem<ECORR_ELEM_F16>::type>(P, nx, B, s16, stream);
+            else if (fmap_format == ECORR_ELEM_BF16) launch_pack<InElem<ECORR_ELEM_BF16>::type>(P, nx, B, s16, stream);
+            else launch_pack<float>(P, nx, B, s16, stream);
         }
         if (!(stages & 2)) return hip_status();
         const dim3 grid((unsigned)ntiles);

@@ -32,6 +32,7 @@
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "out_elem.h"
 #include "split_f16.h"
 
 #include <algorithm>
@@ -96,7 +97,13 @@ __global__ __launch_bounds__(SNT) void split_pack_kernel(const float* __restrict
 // weight).  It is no third template parameter because that would rename the two forward kernels,
 // whose mangled names tests/test_isa_waits.py looks up; with the flag clear they compile to the
 // instructions they had before (profiles/motion_backward/isa_identity.txt).
+// The output element rides there too, for the same reason: PDF | kOutF16 / kOutBF16 makes `out` a
+// [B][O][Q] array of 2-byte elements (ecorr_conv1x1_relu_split_as; non-presplit only) and the
+// epilogue store one range-checked 2-byte buffer store per (channel, query) of out_elem's convert
+// of the fp32 value (out_elem.h) -- lane = query as before, row o starting at byte 2 o Q, so
+// neighbouring queries are not packed into dwords.
 constexpr int kNoRelu = 0x100;
+constexpr int kOutF16 = 0x200, kOutBF16 = 0x400;
 template <int PDF, bool PRE = false>
 __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restrict__ in, int C, int Q,
                                                             const float* __restrict__ qmax, int G,
@@ -106,6 +113,9 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
                                                             const int* __restrict__ scale) {
     constexpr int PD = PDF & 0xff;
     constexpr bool RELU = !(PDF & kNoRelu);
+    constexpr int FMT = (PDF & kOutF16) ? ECORR_OUT_F16 : (PDF & kOutBF16) ? ECORR_OUT_BF16 : ECORR_OUT_F32;
+    static_assert(FMT == ECORR_OUT_F32 || !PRE, "16-bit output: the non-presplit kernel only");
+    constexpr int ES = sizeof(typename OutElem<FMT>::type);   // output element bytes
     constexpr int NB = 3;
     // ALL LDS in one object: with a second __shared__ object hipcc waits vmcnt(0) before every
     // ds_read while an LDS-DMA is in flight (cdna_hip_programming.md, the second-__shared__ trap)
@@ -308,9 +318,10 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
         if (c + k < nkc) step(c + k, bv[k], bv[(k + PD) % (PD + 1)], true);
 
     // ---- epilogue: lane holds query q, channels 32 rb + 8 (r >> 2) + 4 kh + (r & 3)
-    const __amdgpu_buffer_rsrc_t osrc = __builtin_amdgcn_make_buffer_rsrc(out + (int64_t)b * O * Q, 0, O * Q * 4,
-                                                                          0x00020000);
-    const int obase = (qok ? q : O * Q) * 4;
+    const __amdgpu_buffer_rsrc_t osrc = __builtin_amdgcn_make_buffer_rsrc(
+        reinterpret_cast<typename OutElem<FMT>::type*>(out) + (int64_t)b * O * Q, 0, O * Q * ES, 0x00020000);
+    const int obase = (qok ? q : O * Q) * ES;
+    const int os = Q * ES;   // bytes per output row
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -323,22 +334,22 @@ __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restr
                 float v = ldexpf(acc[i][4 * g + t], -(eo[t] + eq));
                 v = v + bo[t];   // a missing bias is 0 (v + 0 = v for every v but -0, which ReLU maps to 0)
                 if constexpr (RELU) v = v < 0.f ? 0.f : v;   // torch.relu: NaN stays NaN
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), osrc, obase + (ob * SO + ol + t) * qs, 0,
-                                                      2);   // nt: 52.2 vs 53.9 us (r4l_ab_conv.txt)
+                store_out<FMT, 2>(v, osrc, obase + (ob * SO + ol + t) * os, 0);   // nt: 52.2 vs 53.9 us (r4l_ab_conv.txt)
             }
         }
 }
 
 constexpr int kConvPD = 2;   // query-column prefetch distance (chunks)
 
-// the split kernels' limits for in float[B][C][Q] -> out float[B][O][Q] with G partial maxima (0: none)
-bool split_geometry_ok(int B, int C, int Q, int O, int G) {
+// the split kernels' limits for in float[B][C][Q] -> out [B][O][Q] of `elem`-byte elements with G partial
+// maxima (0: none)
+bool split_geometry_ok(int B, int C, int Q, int O, int G, int elem = 4) {
     if (G && (G < 0 || (int64_t)G * Q * 4 >= 0x7fffffffLL)) return false;
     if (B <= 0 || C <= 0 || Q <= 0 || O <= 0 || B > 65535 || split_oblocks(O) > 65535) return false;
     // 32-bit buffer offsets: a lane past Q reads from C*Q on, the prefetch reaches 3 chunks past C; the stores
     // likewise from O*Q up to the output block's last row
     return (int64_t)(2 * C + 4 * SKC) * Q * 4 < 0x7fffffffLL &&
-           (int64_t)(O + split_oblocks(O) * SO) * Q * 4 < 0x7fffffffLL;
+           (int64_t)(O + split_oblocks(O) * SO) * Q * elem < 0x7fffffffLL;
 }
 
 }  // namespace
@@ -358,13 +369,22 @@ int launch_conv1x1_split_pack(const float* wt, int O, int C, void* packed, hipSt
 }
 
 int launch_conv1x1_relu_split(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
-                              const float* bias, int O, float* out, hipStream_t stream) {
+                              const float* bias, int O, float* out, hipStream_t stream, int out_format) {
     if (qmax && G <= 0) return ECORR_EINVAL;
-    if (!split_geometry_ok(B, C, Q, O, qmax ? G : 0)) return ECORR_EINVAL;
+    const bool half = out_format == ECORR_OUT_F16 || out_format == ECORR_OUT_BF16;
+    if (!split_geometry_ok(B, C, Q, O, qmax ? G : 0, half ? 2 : 4)) return ECORR_EINVAL;
     if ((const void*)in == (const void*)out) return ECORR_EINVAL;
+    if (!half && out_format != ECORR_OUT_F32) return ECORR_EINVAL;
     const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
-    hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax, G,
-                       (const char*)packed, bias, O, out, nullptr);
+    if (out_format == ECORR_OUT_F16)
+        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD | kOutF16, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax,
+                           G, (const char*)packed, bias, O, out, nullptr);
+    else if (out_format == ECORR_OUT_BF16)
+        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD | kOutBF16, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax,
+                           G, (const char*)packed, bias, O, out, nullptr);
+    else
+        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax, G,
+                           (const char*)packed, bias, O, out, nullptr);
     return hip_status();
 }
 

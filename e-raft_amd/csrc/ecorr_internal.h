@@ -54,7 +54,7 @@ inline void level_table(const PyrGeom& g, F* base, LevelTable<F>* T) {
 }
 
 struct BuildParams : LevelTable<float> {   // the table: the levels written (those the GEMM epilogue fuses: < fused_levels)
-    const float* f1;
+    const float* f1;    // (elements of the launch's fmap_format when that is 16-bit: launch_build)
     const float* f2;
     int D, H, W;
     int q_count;        // query pixels in the fmap1 slab
@@ -77,8 +77,9 @@ struct BuildParams : LevelTable<float> {   // the table: the levels written (tho
 };
 
 // stages (split build only; the fp32 build is one launch): 1 = operand pass, 2 = GEMM + fused
-// pyramid (+ levels > 4), 3 = both
-int launch_build(const BuildParams& P, int B, const PyrGeom& g, float* pyramid, hipStream_t stream, int stages = 3);
+// pyramid (+ levels > 4), 3 = both.  fmap_format (split build, stage 1): ECORR_ELEM_* of P.f1 / P.f2
+int launch_build(const BuildParams& P, int B, const PyrGeom& g, float* pyramid, hipStream_t stream, int stages = 3,
+                 int fmap_format = ECORR_ELEM_F32);
 int64_t build_split_workspace_bytes(int B, int D, int H, int W, int q_count);
 
 struct LookupParams : LevelTable<const float> {   // the table: the pyramid (read only)
@@ -122,8 +123,9 @@ int launch_lookup_backward(const LookupGradParams& P, int B, hipStream_t stream)
 // the fold over L's levels, then the GEMMs whose output is non-null
 int launch_build_backward(const LookupGradParams& L, const BuildGradParams& P, int B, hipStream_t stream);
 
+// out_format: ECORR_OUT_* of out (the 16-bit formats: the packed form only)
 int launch_lookup_conv(const LookupParams& P, int B, const float* wt, const float* bias, int O, float* out,
-                       hipStream_t stream, bool packed);
+                       hipStream_t stream, bool packed, int out_format = ECORR_OUT_F32);
 int64_t conv1x1_packed_floats(int O, int C);
 int launch_conv1x1_pack(const float* wt, int O, int C, float* packed, hipStream_t stream);
 // conv.hip: split-f16 1x1 conv + ReLU on an NCHW tensor (ecorr_conv1x1_relu_split)
@@ -132,8 +134,10 @@ int64_t conv1x1_split_bytes(int O, int C);
 int launch_conv1x1_split_pack(const float* wt, int O, int C, void* packed, hipStream_t stream, int perm_levels = 0);
 // the presplit pack's byte count (its K = presplit_positions(levels))
 int64_t conv1x1_presplit_bytes(int O, int levels);
+// out_format: ECORR_OUT_* of out ([B][O][Q] elements of it)
 int launch_conv1x1_relu_split(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
-                              const float* bias, int O, float* out, hipStream_t stream);
+                              const float* bias, int O, float* out, hipStream_t stream,
+                              int out_format = ECORR_OUT_F32);
 // the same product without bias and ReLU, qmax required (grad_in of the backward: in = the masked
 // gradient, packed = the transposed weight's pack); and whether a geometry is within both kernels'
 // limits (G partial maxima, 0 = none)

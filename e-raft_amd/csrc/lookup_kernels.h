@@ -8,6 +8,7 @@
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
 #include "lookup_stage.h"
+#include "out_elem.h"
 #include "split_f16.h"
 
 namespace ecorr {
@@ -30,42 +31,8 @@ inline bool lookup_takes_cols(const LookupParams& P, int elem, bool* pair) {
 
 namespace {   // the kernels and their dispatch: one copy per including translation unit
 
-// The output element (ecorr_lookup_as, include/ecorr.h): FMT = ECORR_OUT_F32 stores the fp32 sample
-// itself; ECORR_OUT_F16 / ECORR_OUT_BF16 store it rounded once to nearest-even as a 2-byte bit
-// pattern -- f16: the hardware convert of the fp32 sample (overflow -> +-inf, subnormals kept); bf16:
-// NaN stays NaN.
-// The element order [B][C][q_count] is the same, so every offset scales by the element size.
-template <int FMT>
-struct OutElem {
-    static_assert(FMT == ECORR_OUT_F16 || FMT == ECORR_OUT_BF16, "unknown output format");
-    using type = unsigned short;
-};
-template <>
-struct OutElem<ECORR_OUT_F32> {
-    using type = float;
-};
-template <int FMT>
-__device__ __forceinline__ typename OutElem<FMT>::type out_elem(float v) {
-    if constexpr (FMT == ECORR_OUT_F16) {
-        // the sample as an fp32 register first: without this the compiler folds the blend's last fma
-        // into the convert (v_fma_mixlo_f16), which rounds the unrounded sum -- once, but not the fp32
-        // sample: it differs from ecorr_lookup's value cast to f16 wherever that value is an exact tie
-        asm("" : "+v"(v));
-        return __builtin_bit_cast(unsigned short, (_Float16)v);
-    }
-    else if constexpr (FMT == ECORR_OUT_BF16)
-        return __builtin_bit_cast(unsigned short, (__bf16)v);
-    else
-        return v;
-}
-// ... and its buffer store at voff + soff (bytes) of rsrc: one dword, or one 2-byte element
-template <int FMT, int AUX>
-__device__ __forceinline__ void store_out(float v, __amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-    if constexpr (FMT == ECORR_OUT_F32)
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc, voff, soff, AUX);
-    else
-        __builtin_amdgcn_raw_buffer_store_b16((short)out_elem<FMT>(v), rsrc, voff, soff, AUX);
-}
+// The output element OutElem<FMT>, its convert out_elem<FMT> and its buffer store store_out<FMT, AUX>
+// (ecorr_lookup_as, include/ecorr.h): out_elem.h, the one definition of every 16-bit store.
 
 // QB queries per workgroup, 4 threads per query (NTQ = 4 * QB threads); QB = 64 -> 4 waves,
 // QB = 16 -> one wave per workgroup (no cross-wave barrier; waves overlap phases freely).

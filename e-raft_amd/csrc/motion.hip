@@ -28,6 +28,7 @@
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
 #include "lookup_stage.h"
+#include "out_elem.h"
 #include "split_f16.h"
 
 #include <algorithm>
@@ -68,7 +69,9 @@ __global__ __launch_bounds__(NTM) void pack_weight_kernel(const float* __restric
 
 // PAIR (every level width even): windows staged as 8-byte column pairs (lookup_stage.h).
 // PACKED: wt is the packed weight above; else the conv weight [O][C] as stored.
-template <int R, bool PAIR, bool PACKED>
+// FMT (ECORR_OUT_*; ecorr_lookup_conv1x1_relu_packed_as): `out` holds [B][O][q_count] elements of it,
+// the epilogue stores out_elem's convert of the fp32 value (out_elem.h), lane = query as before.
+template <int R, bool PAIR, bool PACKED, int FMT = ECORR_OUT_F32>
 __global__ __launch_bounds__(NTM, 2) void lookup_conv_kernel(LookupParams P, const float* __restrict__ wt,
                                                              const float* __restrict__ bias, int O,
                                                              float* __restrict__ out) {
@@ -191,7 +194,8 @@ __global__ __launch_bounds__(NTM, 2) void lookup_conv_kernel(LookupParams P, con
                     const int o = ob + 32 * i + orow;
                     if (o < O) {
                         const float v = __fadd_rn(i == 0 ? acc0[r] : acc1[r], bias ? bias[o] : 0.0f);
-                        out[((int64_t)b * O + o) * P.q_count + q] = v < 0.0f ? 0.0f : v;   // NaN stays NaN
+                        reinterpret_cast<typename OutElem<FMT>::type*>(out)[((int64_t)b * O + o) * P.q_count + q] =
+                            out_elem<FMT>(v < 0.0f ? 0.0f : v);   // NaN stays NaN
                     }
                 }
             }
@@ -212,15 +216,23 @@ int launch_conv1x1_pack(const float* wt, int O, int C, float* packed, hipStream_
 }
 
 int launch_lookup_conv(const LookupParams& P, int B, const float* wt, const float* bias, int O, float* out,
-                       hipStream_t stream, bool packed) {
+                       hipStream_t stream, bool packed, int out_format) {
     if (P.radius != 4) return ECORR_ERADIUS;
     if (P.levels > 4) return ECORR_ELEVELS;
     if (O <= 0 || O % OW != 0) return ECORR_EINVAL;
     if (packed && conv1x1_packed_floats(O, P.C) * 4 >= 0x7fffffffLL) return ECORR_EINVAL;
     const dim3 grid((unsigned)((P.q_count + QBM - 1) / QBM), (unsigned)B), block(NTM);
+    if (out_format != ECORR_OUT_F32 && (!packed || (out_format != ECORR_OUT_F16 && out_format != ECORR_OUT_BF16)))
+        return ECORR_EINVAL;
     bool pair = true;   // column-pair staging: every level width even, 8-byte aligned levels
     for (int lv = 0; lv < P.levels; ++lv) pair &= P.lw[lv] % 2 == 0 && (uintptr_t)P.lvl[lv] % 8 == 0;
-    if (packed) {
+    if (out_format == ECORR_OUT_F16) {
+        if (pair) hipLaunchKernelGGL((lookup_conv_kernel<4, true, true, ECORR_OUT_F16>), grid, block, 0, stream, P, wt, bias, O, out);
+        else hipLaunchKernelGGL((lookup_conv_kernel<4, false, true, ECORR_OUT_F16>), grid, block, 0, stream, P, wt, bias, O, out);
+    } else if (out_format == ECORR_OUT_BF16) {
+        if (pair) hipLaunchKernelGGL((lookup_conv_kernel<4, true, true, ECORR_OUT_BF16>), grid, block, 0, stream, P, wt, bias, O, out);
+        else hipLaunchKernelGGL((lookup_conv_kernel<4, false, true, ECORR_OUT_BF16>), grid, block, 0, stream, P, wt, bias, O, out);
+    } else if (packed) {
         if (pair) hipLaunchKernelGGL((lookup_conv_kernel<4, true, true>), grid, block, 0, stream, P, wt, bias, O, out);
         else hipLaunchKernelGGL((lookup_conv_kernel<4, false, true>), grid, block, 0, stream, P, wt, bias, O, out);
     } else {

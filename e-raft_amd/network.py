@@ -197,13 +197,17 @@ class ERAFT(nn.Module):
     convc1 train through it; under torch.no_grad() its predictions are bitwise fuse_motion_corr's.
     mixed_precision=True is the reference's mixed-precision path (eraft.py:101, 110-117, 131-132, which
     its get_args() switches off): fnet, cnet and the update block run under
-    torch.autocast("cuda", dtype=amp_dtype) (torch.float16 or torch.bfloat16), the fmaps go back to
-    fp32 for the CorrBlock, coords and predictions stay fp32, and the lookup is asked for amp_dtype
-    directly (corr_fn(coords1, out_dtype=amp_dtype): the kernel stores what autocast's cast in front
-    of convc1 would produce, bit for bit).  It composes with fuse_motion_corr,
-    differentiable_corr and train_motion_corr (lookup_conv1x1_relu keeps its fp32 output);
-    hip_upsample gets the mask as fp32.  _native_half_lookup=False (private: the A/B arm of the tests
-    and tools/bench_lookup_half.py) takes the fp32 lookup and lets autocast cast it.
+    torch.autocast("cuda", dtype=amp_dtype) (torch.float16 or torch.bfloat16), coords and predictions
+    stay fp32, and the CorrBlock is 16-bit at both ends: fnet's amp_dtype fmaps go to
+    CorrBlock(..., fmap_dtype=amp_dtype) as they are (the split build reads them itself: bitwise the
+    pyramid of their .float()), the lookup is asked for amp_dtype directly (corr_fn(coords1,
+    out_dtype=amp_dtype): the kernel stores what autocast's cast in front of convc1 would produce, bit
+    for bit), and with fuse_motion_corr / train_motion_corr lookup_conv1x1_relu(..., out_dtype=amp_dtype)
+    stores what autocast's cast in front of convc2 would produce.  It composes with fuse_motion_corr,
+    differentiable_corr and train_motion_corr; hip_upsample gets the mask as fp32.
+    _native_half_lookup=False (private: the A/B arm of the tests, tools/bench_lookup_half.py and
+    tools/bench_half_io.py) is the whole path without any of the three: the fmaps go back to fp32
+    (.float()), the lookup and lookup_conv1x1_relu return fp32 and autocast casts them.
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
@@ -272,16 +276,21 @@ class ERAFT(nn.Module):
         image2 = self.image_padder.pad(image2).contiguous()
         with self._autocast():
             fmap1, fmap2 = self.fnet([image1, image2])
-        # differentiable_corr: gradients reach fnet through the HIP backward (corr.py); the keyword
-        # is passed only then, so a reference-signature CorrBlock can stand in otherwise
-        corr_fn = CorrBlock(fmap1.float().contiguous(), fmap2.float().contiguous(),
-                            num_levels=self.corr_levels, radius=self.corr_radius,
-                            **({"differentiable": True} if self.differentiable_corr else {}))
+        # mixed precision: the block reads fnet's amp_dtype fmaps itself and the lookup (or the fused
+        # convc1) stores amp_dtype itself, what autocast would cast it to for convc1 (convc2)
+        half_lookup = self.mixed_precision and self._native_half_lookup
+        # differentiable_corr: gradients reach fnet through the HIP backward (corr.py); the keywords
+        # are passed only on their paths, so a reference-signature CorrBlock can stand in otherwise
+        kw = {"differentiable": True} if self.differentiable_corr else {}
+        if half_lookup and fmap1.dtype == self.amp_dtype and fmap2.dtype == self.amp_dtype:
+            corr_fn = CorrBlock(fmap1.contiguous(), fmap2.contiguous(), num_levels=self.corr_levels,
+                                radius=self.corr_radius, fmap_dtype=self.amp_dtype, **kw)
+        else:
+            corr_fn = CorrBlock(fmap1.float().contiguous(), fmap2.float().contiguous(),
+                                num_levels=self.corr_levels, radius=self.corr_radius, **kw)
         with self._autocast():
             net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
             net, inp = torch.tanh(net), torch.relu(inp)
-        # mixed precision: the lookup stores amp_dtype itself, what autocast would cast it to for convc1
-        half_lookup = self.mixed_precision and self._native_half_lookup
         coords0, coords1 = self.initialize_flow(image1)
         if flow_init is not None:
             coords1 = coords1 + flow_init
@@ -290,7 +299,8 @@ class ERAFT(nn.Module):
             coords1 = coords1.detach()
             if self.fuse_motion_corr:
                 c1 = self.update_block.encoder.convc1
-                corr = corr_fn.lookup_conv1x1_relu(coords1, c1.weight, c1.bias)
+                corr = corr_fn.lookup_conv1x1_relu(coords1, c1.weight, c1.bias,
+                                                   **({"out_dtype": self.amp_dtype} if half_lookup else {}))
             elif half_lookup:
                 corr = corr_fn(coords1, out_dtype=self.amp_dtype)
             else:

@@ -122,6 +122,33 @@ int ecorr_lookup(const float* pyramid, const float* coords, int B, int H, int W,
 int ecorr_lookup_as(const float* pyramid, const float* coords, int B, int H, int W, int q_count,
                     int levels, int radius, int out_format, void* out, void* stream);
 
+/* The same three element codes under a name that also reads sensibly for an INPUT format (the
+ * values are the ECORR_OUT_* ones: either spelling may be passed to any *_as entry). */
+#define ECORR_ELEM_F32 ECORR_OUT_F32
+#define ECORR_ELEM_F16 ECORR_OUT_F16
+#define ECORR_ELEM_BF16 ECORR_OUT_BF16
+
+/* 16-bit feature maps in (added within ABI 17: purely additive, the version stays 17):
+ * ecorr_build_split_pack / ecorr_build_split reading fmap1 and fmap2 as elements of fmap_format --
+ * float (ECORR_ELEM_F32: the existing launch), IEEE binary16 (ECORR_ELEM_F16) or bfloat16
+ * (ECORR_ELEM_BF16); both fmaps have the same format, the same shapes and order as the fp32 entries
+ * take, and need only the element's alignment (a 16-bit query slab view may be 2-byte aligned only).
+ * Same workspace size (ecorr_build_split_workspace_size), same geometry contract;
+ * ecorr_build_split_gemm follows ecorr_build_split_pack_as unchanged.
+ * Bitwise contract: the kernel converts each element to fp32 on load, which is exact, and runs the
+ * fp32 operand pass on it, so the workspace contents -- exponents and hi/lo panels -- are bitwise
+ * those of ecorr_build_split_pack on the fmaps converted to fp32; the pyramid of the gemm that follows
+ * is therefore bitwise equal too, and a +-inf or NaN element behaves as the same fp32 value does
+ * (+-inf -> NaN in its level-0 row / column, NaN -> NaN).
+ * Same argument validation and error codes as the fp32 entries; an unknown fmap_format gives
+ * ECORR_EINVAL after those checks and before any launch.  ecorr_build_split_as is pack_as then gemm,
+ * as ecorr_build_split is pack then gemm.  (The fp32-MFMA build, ecorr_build, takes fp32 only.)
+ * Replaces: the .float() of both fmaps (eraft.py:104-105) + CorrBlock.__init__ (corr.py:13-27). */
+int ecorr_build_split_pack_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
+                              int q_count, void* workspace, void* stream);
+int ecorr_build_split_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
+                         int q_count, int levels, float* pyramid, void* workspace, void* stream);
+
 /* ---- The backward (ABI 17): gradients of a loss through ecorr_lookup and ecorr_build, coordinates detached ----
  * Deterministic: a query row's gradient images are owned by one workgroup per launch and summed in
  * a fixed order; there are no float atomics, so equal inputs give bitwise equal gradients. */
@@ -194,6 +221,25 @@ int ecorr_conv1x1_split_size(int O, int C, int64_t* bytes);
 int ecorr_conv1x1_split_pack(const float* weight, int O, int C, void* packed, void* stream);
 int ecorr_conv1x1_relu_split(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
                              const float* bias, int O, float* out, void* stream);
+
+/* 16-bit convc1 output (added within ABI 17: purely additive, the version stays 17):
+ * ecorr_conv1x1_relu_split / ecorr_lookup_conv1x1_relu_packed with a chosen output element.  out holds
+ * B*O*Q (B*O*q_count) elements of out_format (ECORR_OUT_* / ECORR_ELEM_*) in the same [B][O][Q] order,
+ * 2-byte aligned for the 16-bit formats.  Bitwise contract: each element is the fp32 value the fp32
+ * entry writes -- after bias and ReLU -- rounded ONCE to nearest-even by the rules of ecorr_lookup_as
+ * (binary16: the hardware convert, overflow to +-inf, subnormals kept; bfloat16: on the upper 16 bits),
+ * so the result is bitwise a cast of the fp32 entry's output, which autocast would otherwise make in a
+ * kernel of its own in front of convc2 (update.py:75).  The non-finite contract is unchanged (a NaN
+ * stays NaN).  ECORR_OUT_F32 is the existing launch.  in != out still holds, and the 32-bit offset
+ * limit of the stores scales with the element size.  Same argument validation and error codes as the
+ * fp32 entries; an unknown out_format gives ECORR_EINVAL after those checks and before any launch.
+ * (The presplit conv and the unpacked fused entry have no _as form.)
+ * Replaces: F.relu(self.convc1(corr)) (update.py:67,74) followed by autocast's cast. */
+int ecorr_conv1x1_relu_split_as(const float* in, int B, int C, int Q, const float* qmax, int G, const void* packed,
+                                const float* bias, int O, int out_format, void* out, void* stream);
+int ecorr_lookup_conv1x1_relu_packed_as(const float* pyramid, const float* coords, int B, int H, int W,
+                                        int q_count, int levels, int radius, const float* packed,
+                                        const float* bias, int O, int out_format, void* out, void* stream);
 
 /* The backward of ecorr_conv1x1_relu_split's function (added within ABI 17), for any in float[B][C][Q]:
  * with grad_out, out float[B][O][Q] (out: the forward's post-ReLU result) and the masked gradient
