@@ -9,6 +9,15 @@ fp64 oracle stands in for it here (the reference's own values are checked in tes
 split build must also be at least as accurate as the fp32 one on every case, including operands
 scaled far from 1 (the per-pixel scales) and ragged shapes (the non-vector staging path, D not a
 multiple of the 16-deep K chunk).  Pooled levels stay bit-exact from either level 0.
+
+The cases here are the precision cases: D in {256, 100, 64}, six shapes, operand scales and the
+split's limits.  Which kernel of launch_build a shape reaches is swept elsewhere:
+tests/test_build_sweep_gpu.py (cases and the dispatch restated in tests/build_cases.py) runs every
+instantiation against the oracle -- build_split16_kernel<!MUL> (D = 241 .. 255), build_split_kernel at
+D < 16, 16, 17 and with the operand pass's re-read path (D > 256), build_kernel<true, true>,
+build_kernel<true, false> (operands of 2 GiB), build_kernel<false, false> chosen by W, by the slab and by
+a misaligned fmap, build_f32_kernel on a slab that is not whole rows -- over tile geometry, levels 1 - 4
+and batch sizes, bit for bit on integer inputs.
 """
 import numpy as np
 import pytest

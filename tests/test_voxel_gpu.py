@@ -20,7 +20,7 @@ NORM_TOL = 1e-6   # rtol and atol on the normalized grid
 @pytest.fixture(scope="module")
 def ea():
     if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
+        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
     import eraft_amd
     eraft_amd.lib()
     return eraft_amd
