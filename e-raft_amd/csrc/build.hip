@@ -21,10 +21,13 @@
 // Pooling is bit-exact given the same level 0 in both; per-element accumulation order does not
 // depend on the tiling, so query-slab (row-sharded) builds are bitwise the whole build's rows.
 //
+// What is a property of the tile and not of one kernel -- tile geometry and order, level addressing,
+// the 256 x 128 kernels' LDS array, exponents, panel descriptors, scale step and stores -- is in
+// build_tile.h; this file is the one translation unit that includes it.
+//
 // There are no runtime knobs: every variant that lost an A/B is gone from the source (DESIGN.md
 // §3.1 keeps the record); lab builds for new A/Bs are separate .so files (tools/).
-#include "ecorr_device.h"
-#include "ecorr_internal.h"
+#include "build_tile.h"
 #include "out_elem.h"
 #include "split_f16.h"
 
@@ -34,100 +37,7 @@ namespace ecorr {
 
 namespace {
 
-constexpr int TBH = 8, TBW = 16;  // regular target block (rows x cols) of one n-tile
-constexpr int PANEL = 8192;       // bytes of one (128-pixel tile, 16-deep K chunk) operand panel
-
-__device__ __forceinline__ float pool4(float a, float b, float c, float d) {
-    return __fmul_rn(__fadd_rn(__fadd_rn(__fadd_rn(a, b), c), d), 0.25f);
-}
-
-// pool4 as four VALU ops in the same order: left to itself hipcc pairs the split epilogue's pools
-// into v_pk_add_f32 whose operands sit in different register pairs (two v_mov per packed add)
-__device__ __forceinline__ float pool4_v(float a, float b, float c, float d) {
-    float s;
-    asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(a), "v"(b));
-    asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(s), "v"(c));
-    asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(s), "v"(d));
-    asm("v_mul_f32 %0, 0.25, %1" : "=v"(s) : "v"(s));
-    return s;
-}
-
-// Bijective XCD-aware remap (cdna_hip_programming.md §5 T1): consecutive logical tiles land on
-// one XCD so tiles sharing operand panels share that XCD's L2.  Speed only, never correctness.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
-// n-tiles: 8 x 16 target blocks (regular), or, in the last 4 rows when H % 8 is 1..4, 4 x 32
-// blocks ("band"): those rows feed pyramid levels 0-2 only (level 3 of an H = 8k + r map, r <= 4,
-// has k rows), so the band pools 4 x 8 sub-blocks and no 8-row tile row is padded half empty
-// (DSEC H = 60: 6.7% of the matrix work saved).
-struct NTile { int ty0, tx0, band; };
-__device__ __forceinline__ NTile ntile_of(const BuildParams& P, int nt) {
-    NTile n;
-    if (nt < P.n_reg) {
-        const int nty = nt / P.n_ntx;
-        n.ty0 = nty * TBH;
-        n.tx0 = (nt - nty * P.n_ntx) * TBW;
-        n.band = 0;
-    } else {
-        n.ty0 = P.band_y0;
-        n.tx0 = (nt - P.n_reg) * 32;
-        n.band = 1;
-    }
-    return n;
-}
-
-// Grouped tile order: GM m-tiles x all n-tiles per group, so consecutive tiles share panels.  BAL:
-// the item's m-tiles split into ceil(n_m / GM) groups of (nearly) equal size instead of full groups
-// and a remainder -- at DSEC (19 split16 query tiles) GM 10 makes two groups (10, 9), so every
-// target panel leaves the L2 twice per item instead of three times (8, 8, 3): FETCH -20%, the build
-// 1.3% shorter (profiles/r05_lab/gm_clock_l2_b.txt); 10 query panels (2.5 MB) + the resident
-// blocks' target panels still fit an XCD's 4-MB L2 (GM 16 does not: 4.5 MB, slower).
-template <int GM, bool BAL>
-__device__ __forceinline__ void decode_tile(const BuildParams& P, int t, int n_m, int& b, int& mt, int& nt) {
-    const int per_b = n_m * P.n_nt;
-    b = t / per_b;
-    const int i = t - b * per_b;
-    const int ng = (n_m + GM - 1) / GM;
-    const int gm = BAL ? (n_m + ng - 1) / ng : GM;
-    const int gsz = gm * P.n_nt;
-    const int grp = i / gsz, gi = i - grp * gsz;
-    const int first_m = grp * gm;
-    const int gsm = min(n_m - first_m, gm);
-    mt = first_m + gi % gsm;
-    nt = gi / gsm;
-}
 constexpr int kGM16 = 10;   // build_split16_kernel's group bound (balanced); the other builds: 8
-
-// One pooled-level pixel (row, col) of a query image: tiled (ntx > 0; the tile must exist, cells
-// in a tile's padding are written and never read), interleaved (ntx < 0; likewise the block) or
-// compact row-major (range-checked).
-__device__ __forceinline__ float* level_px(const BuildParams& P, int L, int64_t row_img, int r, int c) {
-    if (P.lntx[L] < 0) {   // interleaved: the block must exist
-        if (!ilv_cell_in(r, c, L, P.lnty[L], -P.lntx[L])) return nullptr;
-        return P.lvl[L] + pix_off(row_img, r, c, L, P.lntx[L], P.lw[L], P.lsz[L]);
-    }
-    float* img = P.lvl[L] + row_img * P.lsz[L];
-    if (P.lntx[L] > 0) {
-        if ((r >> 2) >= P.lnty[L] || (c >> 3) >= P.lntx[L]) return nullptr;
-        return img + tiled_off(r, c, P.lntx[L]);
-    }
-    if (r >= P.lh[L] || c >= P.lw[L]) return nullptr;
-    return img + (int64_t)r * P.lw[L] + c;
-}
-
-// Buffer descriptor over the slab of fused level lv that holds the query images [rows0, rows0 + nq)
-// (ecorr_device.h slab_first / slab_bytes): its range check is the query bound.  lv >= 1: the fused
-// levels that are interleaved.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t level_rsrc(const BuildParams& P, int lv, int64_t rows0, int nq) {
-    if (lv >= 1)
-        return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + slab_first(true, rows0, P.lsz[lv]), 0,
-                                                 (int)slab_bytes(true, rows0, nq, P.lsz[lv]), 0x00020000);
-    return __builtin_amdgcn_make_buffer_rsrc(P.lvl[lv] + slab_first(false, rows0, P.lsz[lv]), 0,
-                                             (int)slab_bytes(false, rows0, nq, P.lsz[lv]), 0x00020000);
-}
 
 // ============================================================================================
 // Split GEMM (default).  Block tile: 256 queries (two 128-query fmap1 panels) x one 128-target
@@ -158,29 +68,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t level_rsrc(const BuildParams& 
 // level-1 lines pass through a wave-private LDS transpose and leave whole as non-temporal stores
 // (out of L2); levels 2-3 (6% of the bytes) leave as 16- / 8-byte row pieces.
 // ============================================================================================
-constexpr int SQ = 256;                     // queries per split tile
 constexpr int SCHUNK = PANEL;               // LDS bytes per K chunk (the target panel)
 constexpr int SNBUF = 4;                    // LDS buffers of the target panel's chunk ring
 constexpr int SCOPIES = SCHUNK / 1024 / 4;  // LDS-DMA copies per wave per chunk (2)
 constexpr int QLOADS = 4;                   // query fragment loads per wave per chunk (hi, lo x 2 rows)
-constexpr int SLDS = 4 * 4 * 32 * 144;      // LDS bytes: the epilogue's transpose regions (> the K loop's)
-constexpr int SOOB = 0x7ffffff0;            // buffer offset beyond any panel: loads 0, touches nothing
-constexpr int ST_L01 = 2;                   // level-0/1 store cache policy: nt (A/B: 725 vs 731 us for nt sc1;
-                                            // plain and sc1 alone ~1000 us: the lines stay in L2 and evict the panels;
-                                            // split16, round 3: nt 605 vs nt sc1 627 us)
 constexpr int XS = 144;                     // LDS bytes per query of the epilogue's line transpose
 static_assert(4 * 4 * 32 * XS <= SLDS && SNBUF * SCHUNK <= SLDS, "LDS regions");
-
-// target (y, x) of position p of a split fmap2 panel, relative to the n-tile origin
-__host__ __device__ __forceinline__ void split_target(int p, bool band, int& y, int& x) {
-    if (!band) {
-        y = 4 * ((p >> 5) & 1) + ((p >> 3) & 3);
-        x = 8 * (p >> 6) + (p & 7);
-    } else {
-        y = (p >> 3) & 3;
-        x = 8 * (p >> 5) + (p & 7);
-    }
-}
 
 // wait_vm<n> for an n that is a constant once the loop around the call is unrolled
 template <bool LGKM0, int N = 40>
@@ -200,12 +93,13 @@ __device__ __forceinline__ void swap32(float& a, float& b) {
 
 // Epilogue of the split build for one wave: its 64 queries (block-local qw .. qw + 63) x the
 // n-tile tc, from its accumulators (C^T fragments, build_split_kernel); xw = the wave's four
-// LDS transpose regions (4 x 32 x XS bytes); exq = the block's query exponents, ext / fst = the
-// n-tile's negated target exponents and their powers of two.
+// LDS transpose regions (4 x 32 x XS bytes); smem = the block's LDS array with the published
+// exponents (build_tile.h).
 template <bool MUL>
-__device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&acc)[2][4], char* const xw, int qw,
-                                               const int* exq, const int* ext, const float* fst, const NTile& tc,
-                                               int b, int q0, int lane) {
+__device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&acc)[2][4], char* smem, char* const xw,
+                                               int qw, const NTile& tc, int b, int q0, int lane) {
+    const int *exq = tile_exq(smem), *ext = tile_ext(smem);
+    const float* fst = tile_fst(smem);
     const int acol = lane & 31, arow = lane >> 5;
     // Line segments through a wave-private LDS transpose (no barrier: a wave's LDS accesses are
     // processed in order): the lane writes its 16-byte pieces into the line image of its query
@@ -217,10 +111,12 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
     const int m4 = lane & 3, k4 = acol >> 2;
     const int wo = acol * XS, ro = (4 * k4) * XS + 64 * arow + 16 * m4;
     const int L = P.fused_levels;
-    const int64_t rows0 = (int64_t)b * P.q_count + q0;   // the block's first query image
-    const int nq = min(SQ, P.q_count - q0);
     // per-level descriptors over the block's query images (level_rsrc); interleaved levels: over
     // the 64-row groups the block's rows touch, from group g0
+    const int64_t rows0 = (int64_t)b * P.q_count + q0;   // the block's first query image
+    const int nq = min(SQ, P.q_count - q0);
+    __amdgpu_buffer_rsrc_t rl[4];
+    block_levels(P, rows0, nq, rl);
     const int64_t g0 = slab_g0(rows0);
     // read the transposed segments back and store them: line byte offset lo (+ the query image)
     auto store_lines = [&](const char* xp, __amdgpu_buffer_rsrc_t rs, int64_t lsz, int ql, int lo, bool ok) {
@@ -229,9 +125,7 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
         for (int s = 0; s < 4; ++s) pc[s] = *reinterpret_cast<const floatx4*>(xp + ro + s * XS);
         const int base = (int)((ql + 4 * k4) * lsz * 4) + lo + 16 * m4;
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, pc[s]), rs,
-                                                   ok ? base + (int)(s * lsz * 4) : SOOB, 0, ST_L01);
+        for (int s = 0; s < 4; ++s) store_piece_if(rs, ok, base + (int)(s * lsz * 4), pc[s]);
     };
     // One block row (r, c .. c + N - 1), N = the block width, of level 2 or 3 (interleaved) for
     // block-local query qloc: lanes on consecutive queries write consecutive 4N-byte pieces, so a
@@ -239,37 +133,19 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
     // vs 685 us with plain stores, which park the lines in L2).  Queries past the block and
     // blocks outside the level are dropped (padding cells of a block are written, never read).
     auto store_px = [&](__amdgpu_buffer_rsrc_t rs, int lv, int qloc, int r, int c, auto val) {
-        constexpr int N = sizeof(val) / 4;
         const bool in = qloc < nq && ilv_cell_in(r, c, lv, P.lnty[lv], -P.lntx[lv]);
         // row term + cell term, each in 32 bits (summed in 64 bits the epilogue grows by ~200 instructions)
         const int off = ((int)ilv_row_off(rows0 + qloc, g0, lv, P.lsz[lv]) + (int)ilv_cell_off(r, c, lv, -P.lntx[lv])) * 4;
-        if constexpr (N == 4)
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, val), rs, in ? off : SOOB, 0, ST_L01);
-        else
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, val), rs, in ? off : SOOB, 0, ST_L01);
+        store_piece_if(rs, in, off, val);
     };
-    // Scaling: x = acc 2^(nqe + ext) (/ sqrt(D) when that is no power of two).  Where every
-    // exponent of the wave's queries and of the panel's targets lies in [-63, 63], the 2^nqe 2^ext
-    // product is a normal power of two and one multiply by it rounds exactly as ldexpf does: two
-    // packed multiplies per element pair instead of an add, a negate and an ldexp per element.
-    bool fast_scale;
-    {
-        bool ok = ext[lane] >= -63 && ext[lane] <= 63 && ext[lane + 64] >= -63 && ext[lane + 64] <= 63;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int n = -(exq[qw + 32 * i + acol] + (MUL ? P.scale_shift : 0));
-            ok = ok && n >= -63 && n <= 63;
-        }
-        fast_scale = __all(ok);
-    }
-    const __amdgpu_buffer_rsrc_t r0 = level_rsrc(P, 0, rows0, nq);
-    const __amdgpu_buffer_rsrc_t r1 = level_rsrc(P, L > 1 ? 1 : 0, rows0, nq);
-    const __amdgpu_buffer_rsrc_t r2 = level_rsrc(P, L > 2 ? 2 : 0, rows0, nq);
-    const __amdgpu_buffer_rsrc_t r3 = level_rsrc(P, L > 3 ? 3 : 0, rows0, nq);
+    const bool fast = fast_scale<MUL>(P, exq, ext, qw, lane);   // the scale step: build_tile.h
+    // the lane's four targets of a group: one base register, the group in the ds_read's immediate
+    const int* const extl = ext + 4 * arow;
+    const float* const fstl = fst + 4 * arow;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int ql = qw + 32 * i;          // first block-local query of this tile row
-        const int nqe = -(exq[ql + acol] + (MUL ? P.scale_shift : 0));
+        const int nqe = query_exp<MUL>(P, exq, ql + acol);
         // level-1 values of the lane's query: [block bb][row][col pair] (band: [half][2 y1 + jl]);
         // level 2: [bb][row r] (band: [bb][jl]); level 3: [bb]
         float l1[2][4][2], l2[2][2], l3[2];
@@ -278,37 +154,22 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
             // scaled values of lines j = 2 bb + jl, [jl][g4][t]; target exponents
             // ext[32 j + 8 g4 + 4 arow + t]
             float v[2][4][4];
-            if (fast_scale) {
+            // one uniform branch around the eight groups of four, as in split16_epilogue
+            auto acc4 = [&](int j, int g4) {
+                return floatx4{acc[i][j][4 * g4], acc[i][j][4 * g4 + 1], acc[i][j][4 * g4 + 2], acc[i][j][4 * g4 + 3]};
+            };
+            if (fast) {
                 const float sq = exp2i(nqe);
 #pragma unroll
-                for (int jl = 0; jl < 2; ++jl) {
-                    const int j = 2 * bb + jl;
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const floatx4 s4 = *reinterpret_cast<const floatx4*>(fst + 32 * j + 8 * g4 + 4 * arow);
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {   // exact power-of-two products, v_pk_mul_f32 pairs
-                            const floatx2 x = floatx2{acc[i][j][4 * g4 + 2 * h], acc[i][j][4 * g4 + 2 * h + 1]} *
-                                              (floatx2{sq, sq} * floatx2{s4[2 * h], s4[2 * h + 1]});
-                            v[jl][g4][2 * h] = MUL ? x[0] : __fdiv_rn(x[0], P.scale);
-                            v[jl][g4][2 * h + 1] = MUL ? x[1] : __fdiv_rn(x[1], P.scale);
-                        }
-                    }
+                for (int k = 0; k < 8; ++k) {   // k = 4 jl + g4
+                    const int j = 2 * bb + (k >> 2), g4 = k & 3;
+                    scale4_fast<MUL>(P, acc4(j, g4), sq, fstl + 32 * j + 8 * g4, v[k >> 2][g4]);
                 }
             } else {
 #pragma unroll
-                for (int jl = 0; jl < 2; ++jl) {
-                    const int j = 2 * bb + jl;
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int4 e4 = *reinterpret_cast<const int4*>(ext + 32 * j + 8 * g4 + 4 * arow);
-                        const int e[4] = {e4.x, e4.y, e4.z, e4.w};
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const float x = ldexpf(acc[i][j][4 * g4 + t], nqe + e[t]);
-                            v[jl][g4][t] = MUL ? x : __fdiv_rn(x, P.scale);
-                        }
-                    }
+                for (int k = 0; k < 8; ++k) {
+                    const int j = 2 * bb + (k >> 2), g4 = k & 3;
+                    scale4_ldexp<MUL>(P, acc4(j, g4), nqe, extl + 32 * j + 8 * g4, v[k >> 2][g4]);
                 }
             }
             // level 0: line j = rows g4 x this lane's 4 columns
@@ -322,7 +183,7 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
                         floatx4{v[jl][g4][0], v[jl][g4][1], v[jl][g4][2], v[jl][g4][3]};
                 const int tr = (tc.ty0 >> 2) + (tc.band ? 0 : (j & 1));
                 const int tcl = (tc.tx0 >> 3) + (tc.band ? j : (j >> 1));
-                store_lines(xp, r0, P.lsz[0], ql, tile_base(tr, tcl, P.lntx[0]) * 4 + 64 * arow,
+                store_lines(xp, rl[0], P.lsz[0], ql, tile_base(tr, tcl, P.lntx[0]) * 4 + 64 * arow,
                             tr < P.lnty[0] && tcl < P.lntx[0]);
             }
             if (L < 2) continue;
@@ -377,9 +238,9 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
             }
             const floatx4 row2 = tc.band ? floatx4{l2[0][0], l2[1][0], l2[0][1], l2[1][1]}
                                          : floatx4{l2[0][0], l2[0][1], l2[1][0], l2[1][1]};
-            store_px(r2, 2, ql + acol, (tc.ty0 >> 2) + (tc.band ? 0 : arow), (tc.tx0 >> 2) + (tc.band ? 4 * arow : 0), row2);
+            store_px(rl[2], 2, ql + acol, (tc.ty0 >> 2) + (tc.band ? 0 : arow), (tc.tx0 >> 2) + (tc.band ? 4 * arow : 0), row2);
             if (L >= 4 && !tc.band)   // level 3: the n-tile's 1 x 2 pixels, from the arow-0 lanes
-                store_px(r3, 3, arow ? nq : ql + acol, tc.ty0 >> 3, tc.tx0 >> 3, floatx2{l3[0], l3[1]});
+                store_px(rl[3], 3, arow ? nq : ql + acol, tc.ty0 >> 3, tc.tx0 >> 3, floatx2{l3[0], l3[1]});
         }
         // level 1 (interleaved 2 x 4 blocks): the lane holds cols 2 arow, 2 arow + 1 of each block
         // row; one swap of rows between the arow halves leaves lane acol with row 0 and lane
@@ -401,52 +262,25 @@ __device__ __forceinline__ void split_epilogue(const BuildParams& P, floatx16 (&
                 swap32(x1, y1);
                 const int yb = (tc.ty0 >> 1) + (tc.band ? 0 : 2 * r) + arow;
                 const int xb = (tc.tx0 >> 1) + (tc.band ? 4 * (2 * bb + r) : 4 * bb);
-                store_px(r1, 1, ql + acol, yb, xb, floatx4{x0, x1, y0, y1});
+                store_px(rl[1], 1, ql + acol, yb, xb, floatx4{x0, x1, y0, y1});
             }
     }
 }
 
 template <bool MUL>
 __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
-    // ALL LDS in this one array: a second __shared__ object can make hipcc wait vmcnt(0) before
-    // every ds_read while a buffer_load ... lds is in flight (cdna_hip_programming.md trap 4(a))
-    __shared__ __attribute__((aligned(16))) char smem[SLDS + (SQ + 256) * 4];
-    int* exq = reinterpret_cast<int*>(smem + SLDS);             // exponents of the 256 queries
-    int* ext = exq + SQ;                                        // ... negated, of the 128 panel targets
-    float* fst = reinterpret_cast<float*>(ext + 128);           // 2^ext when |ext| <= 63
+    __shared__ __attribute__((aligned(16))) char smem[TILE_LDS];   // ALL its LDS (build_tile.h)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b, qt, nt;
-    decode_tile<8, false>(P, xcd_remap(blockIdx.x, gridDim.x), P.n_qt, b, qt, nt);
-    const NTile tc = ntile_of(P, nt);
+    const NTile tc = block_tile<8, false>(P, P.n_qt, b, qt, nt);
     const int q0 = qt * SQ;
-    const int H = P.H, W = P.W;
-    const int64_t Q = (int64_t)H * W;
-
-    // per-pixel exponents: only the epilogue reads them, so they load behind the K loop's last
-    // static wait and reach LDS after it (in the prologue, their two dependent global loads with
-    // vmcnt(0) waits delayed every block's first DMA)
-    int eq = 0, et = 0;
-    auto load_exponents = [&]() {
-        eq = q0 + tid < P.q_count ? P.ex1[(int64_t)b * P.q_count + q0 + tid] : 0;
-        if (tid < 128) {
-            int y, x;
-            split_target(tid, tc.band, y, x);
-            y += tc.ty0;
-            x += tc.tx0;
-            et = (y < H && x < W) ? P.ex2[(int64_t)b * Q + (int64_t)y * W + x] : 0;   // negated after the loop
-        }
-    };
 
     // ---- operand panels of this tile: two query panels (adjacent tiles of pk1), one target panel
     const int nk = (P.D + 15) / 16;   // K chunks
     const int64_t pstride = (int64_t)nk * PANEL;   // bytes of one 128-pixel tile's panels
-    const int qp = 2 * qt;
-    const int nqp = min(2, P.n_mt - qp);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(P.pk1 + ((int64_t)b * P.n_mt + qp) * pstride), 0, (int)(nqp * pstride), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(P.pk2 + ((int64_t)b * P.n_nt + nt) * pstride), 0, (int)pstride, 0x00020000);
+    __amdgpu_buffer_rsrc_t rq, rt;
+    panel_rsrc(P, pstride, b, qt, nt, rq, rt);
     // target panel: copy s of this wave = 1-KB piece wave + 4 s of the chunk (lane-linear, as
     // LDS-DMA requires)
     auto issue = [&](int kc) {
@@ -461,18 +295,7 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
     };
 
     floatx16 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    // pin the accumulators to AGPRs: left to its heuristics hipcc keeps them in VGPRs with MFMA
-    // destinations apart from their sources and spills ~100 registers at 2 waves per SIMD
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(acc[i][j]));
+    zero_acc<true>(acc);   // pinned to AGPRs
 
     // query fragments: wave-private (rows 64 wave .. + 63), so they go global -> VGPR directly,
     // one chunk ahead: query panel wave/2, 32-row group 2 (wave&1) + i, [hi | lo] 1 KB each
@@ -584,21 +407,15 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildParams P) {
         PHASE;
     }
 #undef PHASE
-    load_exponents();
+    int eq = 0, et = 0;
+    load_exponents<split_target>(P, tc, b, q0, tid, eq, et);
     wait_vm<0, true>();             // the exponents and the trailing zero chunks have landed, this wave's reads are done ...
-    exq[tid] = eq;
-    if (tid < 128) {
-        ext[tid] = -et;
-        fst[tid] = exp2i(max(-63, min(-et, 63)));
-    }
+    publish_exponents(smem, tid, eq, et);
     __syncthreads();                // ... in every wave: the chunk buffers are the epilogue's scratch
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(acc[i][j]));
+    pin_acc<true>(acc);
 
     // ---------------- epilogue (per wave, from registers) ----------------
-    split_epilogue<MUL>(P, acc, smem + wave * (4 * 32 * XS), wave * 64, exq, ext, fst, tc, b, q0, lane);
+    split_epilogue<MUL>(P, acc, smem, smem + wave * (4 * 32 * XS), wave * 64, tc, b, q0, lane);
 }
 
 // ============================================================================================
@@ -636,20 +453,6 @@ constexpr int S16QL = 8;                        // query fragment loads per wave
 constexpr int S16LS = 144;                      // LDS bytes per level-0 line in the epilogue transpose
 static_assert(S16NB * PANEL16 <= SLDS && 4 * 2 * 64 * S16LS <= SLDS, "split16 LDS regions");
 
-// target (y, x) of position p of a split16 fmap2 panel, relative to the n-tile origin: p = 16 tg +
-// 4 kb + i lies in quadrant kb (regular: rows 4 (kb & 1) .., cols 8 (kb >> 1) ..; band: cols 8 kb ..)
-// at quadrant row tg >> 1, column 4 (tg & 1) + i
-__host__ __device__ __forceinline__ void split16_target(int p, bool band, int& y, int& x) {
-    const int tg = p >> 4, kb = (p >> 2) & 3, i = p & 3;
-    if (!band) {
-        y = 4 * (kb & 1) + (tg >> 1);
-        x = 8 * (kb >> 1) + 4 * (tg & 1) + i;
-    } else {
-        y = tg >> 1;
-        x = 8 * kb + 4 * (tg & 1) + i;
-    }
-}
-
 // VMEM instructions a wave issues after the last piece of t(j) until the wait for t(j) (j >= 1: in
 // mid(j - 1)).  Issue order: prologue t(0) .. t(S16NB - 2), q(0); pair c: q(c + 1) (c + 1 < NCP),
 // then at its mid barrier (c + 1 < NCP) the wait for t(c + 1) and t(c + S16NB - 1) (< NCP).
@@ -680,8 +483,8 @@ static_assert(S16NB != 4 || S16COPIES != 4 || S16QL != 8 ||
 
 // Epilogue of build_split16_kernel for one wave: its 64 queries (block-local qw .. qw + 63) x the
 // n-tile tc from its accumulators acc[qg][tg]; xw = the wave's two LDS transpose regions (2 x 64
-// lines x S16LS bytes).  It runs beside the partner block's K loop, whose MFMAs hold the SIMD's
-// vector issue half the time, so its VALU count is the cost: every address is 32-bit and hoisted
+// lines x S16LS bytes), smem = the block's LDS array with the published exponents.  It runs
+// beside the partner block's K loop, whose MFMAs hold the SIMD's vector issue half the time, so its VALU count is the cost: every address is 32-bit and hoisted
 // out of the query-group loop (the quadrant geometry is the lane's; only the query row changes),
 // and the cross-lane steps are v_permlane16/32_swap.
 // FULL (a whole 256-query tile whose first query row starts a 64-row group, as every tile of the
@@ -689,17 +492,16 @@ static_assert(S16NB != 4 || S16COPIES != 4 || S16QL != 8 ||
 // soffset and a lane's voffset is one constant per store kind (SOOB where its piece lies outside
 // the level) -- no per-store address VALU, compare or select.
 template <bool MUL, bool FULL>
-__device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (&acc)[4][8], char* const xw, int qw,
-                                                 const int* exq, const int* ext, const float* fst, const NTile& tc,
-                                                 int b, int q0, int lane) {
+__device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (&acc)[4][8], char* smem, char* const xw,
+                                                 int qw, const NTile& tc, int b, int q0, int lane) {
+    const int *exq = tile_exq(smem), *ext = tile_ext(smem);
+    const float* fst = tile_fst(smem);
     const int qn = lane & 15, kb = lane >> 4;
     const int L = P.fused_levels;
     const int64_t rows0 = (int64_t)b * P.q_count + q0;   // the block's first query image
     const int nq = min(SQ, P.q_count - q0);
-    const __amdgpu_buffer_rsrc_t r0 = level_rsrc(P, 0, rows0, nq);
-    const __amdgpu_buffer_rsrc_t r1 = level_rsrc(P, L > 1 ? 1 : 0, rows0, nq);
-    const __amdgpu_buffer_rsrc_t r2 = level_rsrc(P, L > 2 ? 2 : 0, rows0, nq);
-    const __amdgpu_buffer_rsrc_t r3 = level_rsrc(P, L > 3 ? 3 : 0, rows0, nq);
+    __amdgpu_buffer_rsrc_t rl[4];
+    block_levels(P, rows0, nq, rl);
     // level-0 line (tile row, tile col) of quadrant k of the n-tile
     auto line_tr = [&](int k) { return (tc.ty0 >> 2) + (tc.band ? 0 : (k & 1)); };
     auto line_tc = [&](int k) { return (tc.tx0 >> 3) + (tc.band ? k : (k >> 1)); };
@@ -741,72 +543,30 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
     // level 3 (regular tiles, stored by the kb = 0 lanes): the tile's 1 x 2 at (ty0 / 8, tx0 / 8)
     const int b3 = (L > 3 && !tc.band && kb == 0) ? ilv_blkoff(3, tc.ty0 >> 3, tc.tx0 >> 3) : -1;
     auto rowoff = [&](int lv, int rr) { return (int)ilv_row_off(rr, 0, lv, P.lsz[L > lv ? lv : 0]); };   // rr: row from the slab's first group
-    auto st4 = [&](__amdgpu_buffer_rsrc_t rs, int off, bool ok, floatx4 v) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, ok ? off : SOOB, 0, ST_L01);
-    };
-    auto st2 = [&](__amdgpu_buffer_rsrc_t rs, int off, bool ok, floatx2 v) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, ok ? off : SOOB, 0, ST_L01);
-    };
     // FULL: lane-constant offsets (query-row term qn of the 16-query group, the lane's piece; FOOB
     // where the piece lies outside the level) plus a wave-uniform term (qg, the store, the wave's
     // 64-row group = its index: rl0 == 0) -- one v_add per store.  The uniform term stays in the
-    // voffset, soffset 0: with it in an SGPR soffset hipcc omits the wait state a 16-byte store needs
-    // before a VALU overwrites its data VGPRs (LLVM assumes that hazard only without an soffset
-    // register), and such a store wrote the next VALU's value (round 3's "lost" rows; round 5,
-    // tools/soff_repro.py; guarded by tests/test_isa_store_hazard.py).
+    // voffset, soffset 0 (store_piece, build_tile.h, has the hazard that forbids the soffset).
     constexpr int FOOB = 0x70000000;   // + any uniform term stays beyond every slab, below 2^31
     const int qwu = __builtin_amdgcn_readfirstlane(qw);   // wave-uniform (qw = 64 wave)
     const int v0 = l0ok ? l0off - qw * l0stride : FOOB;   // + (qw + 16 qg + s) l0stride
     const int v1x = b1x >= 0 ? (rowoff(1, qn) + b1x) * 4 : FOOB, v1y = b1y >= 0 ? (rowoff(1, qn) + b1y) * 4 : FOOB;
     const int v2 = b2 >= 0 ? (rowoff(2, qn) + b2) * 4 : FOOB, v3 = b3 >= 0 ? (rowoff(3, qn) + b3) * 4 : FOOB;
     const int grpw = qwu >> 6;   // FULL: the wave's interleaved group (block-relative)
-    auto fst4 = [&](__amdgpu_buffer_rsrc_t rs, int voff, int uoff, floatx4 v) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, voff + uoff, 0, ST_L01);
-    };
-    auto fst2 = [&](__amdgpu_buffer_rsrc_t rs, int voff, int uoff, floatx2 v) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, ST_L01);
-    };
-    // fast scale: every exponent of the wave's queries and of the panel's targets in [-63, 63]
-    bool fast_scale;
-    {
-        const int n = -(exq[qw + lane] + (MUL ? P.scale_shift : 0));
-        fast_scale = __all(ext[lane] >= -63 && ext[lane] <= 63 && ext[lane + 64] >= -63 && ext[lane + 64] <= 63 &&
-                           n >= -63 && n <= 63);
-    }
+    const bool fast = fast_scale<MUL>(P, exq, ext, qw, lane);   // the scale step: build_tile.h
 #pragma unroll
     for (int qg = 0; qg < 4; ++qg) {
         const int ql = qw + 16 * qg;   // block-local first query of the group
-        const int nqe = -(exq[ql + qn] + (MUL ? P.scale_shift : 0));
+        const int nqe = query_exp<MUL>(P, exq, ql + qn);
         // v[tg][i] = quadrant pixel (tg >> 1, 4 (tg & 1) + i) of query ql + qn, quadrant kb
         float v[8][4];
-        if (fast_scale) {
-            // x = acc 2^nqe 2^ext: exact power-of-two products, as v_pk_mul_f32 pairs (the
-            // library is built without SLP vectorization, which packed the pooling adds at two
-            // v_mov each; packing is spelled out where it pays)
+        if (fast) {
             const float sq = exp2i(nqe);
-            const floatx2 sq2 = {sq, sq};
 #pragma unroll
-            for (int tg = 0; tg < 8; ++tg) {
-                const floatx4 s4 = *reinterpret_cast<const floatx4*>(fst + 16 * tg + 4 * kb);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const floatx2 x = floatx2{acc[qg][tg][2 * h], acc[qg][tg][2 * h + 1]} *
-                                      (sq2 * floatx2{s4[2 * h], s4[2 * h + 1]});
-                    v[tg][2 * h] = MUL ? x[0] : __fdiv_rn(x[0], P.scale);
-                    v[tg][2 * h + 1] = MUL ? x[1] : __fdiv_rn(x[1], P.scale);
-                }
-            }
+            for (int tg = 0; tg < 8; ++tg) scale4_fast<MUL>(P, acc[qg][tg], sq, fst + 16 * tg + 4 * kb, v[tg]);
         } else {
 #pragma unroll
-            for (int tg = 0; tg < 8; ++tg) {
-                const int4 e4 = *reinterpret_cast<const int4*>(ext + 16 * tg + 4 * kb);
-                const int e[4] = {e4.x, e4.y, e4.z, e4.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float x = ldexpf(acc[qg][tg][i], nqe + e[i]);
-                    v[tg][i] = MUL ? x : __fdiv_rn(x, P.scale);
-                }
-            }
+            for (int tg = 0; tg < 8; ++tg) scale4_ldexp<MUL>(P, acc[qg][tg], nqe, ext + 16 * tg + 4 * kb, v[tg]);
         }
         // level 0: the line through the region (a wave's LDS accesses are processed in order, so
         // group qg + 2's writes cannot overtake group qg's reads of the same region)
@@ -819,8 +579,8 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             const floatx4 x = *reinterpret_cast<const floatx4*>(xr + (s + 8 * jl) * S16LS + 16 * pc);
-            if (FULL) fst4(r0, v0, (qwu + 16 * qg + s) * l0stride, x);
-            else st4(r0, l0off + (16 * qg + s) * l0stride, l0ok && l0q + 16 * qg + s < nq, x);
+            if (FULL) store_piece(rl[0], v0, (qwu + 16 * qg + s) * l0stride, x);
+            else store_piece_if(rl[0], l0ok && l0q + 16 * qg + s < nq, l0off + (16 * qg + s) * l0stride, x);
         }
         if (L < 2) continue;
         // this lane's query row in its interleaved group
@@ -851,18 +611,18 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
                 y[c] = __uint_as_float(sw[1]);
             }
             if (FULL) {
-                fst4(r1, v1x, rowoff(1, (grpw << 6) + 16 * qg) * 4, floatx4{x[0], x[1], x[2], x[3]});
-                fst4(r1, v1y, rowoff(1, (grpw << 6) + 16 * qg) * 4, floatx4{y[0], y[1], y[2], y[3]});
+                store_piece(rl[1], v1x, rowoff(1, (grpw << 6) + 16 * qg) * 4, floatx4{x[0], x[1], x[2], x[3]});
+                store_piece(rl[1], v1y, rowoff(1, (grpw << 6) + 16 * qg) * 4, floatx4{y[0], y[1], y[2], y[3]});
             } else {
                 const int base1 = rowoff(1, rr);
-                st4(r1, (base1 + b1x) * 4, qok && b1x >= 0, floatx4{x[0], x[1], x[2], x[3]});
-                st4(r1, (base1 + b1y) * 4, qok && b1y >= 0, floatx4{y[0], y[1], y[2], y[3]});
+                store_piece_if(rl[1], qok && b1x >= 0, (base1 + b1x) * 4, floatx4{x[0], x[1], x[2], x[3]});
+                store_piece_if(rl[1], qok && b1y >= 0, (base1 + b1y) * 4, floatx4{y[0], y[1], y[2], y[3]});
             }
         }
         if (L < 3) continue;
         // level 2: 4 lanes x 8 B = one query's 2 x 4 block (band: half of two)
-        if (FULL) fst2(r2, v2, rowoff(2, (grpw << 6) + 16 * qg) * 4, floatx2{l2[0], l2[1]});
-        else st2(r2, (rowoff(2, rr) + b2) * 4, qok && b2 >= 0, floatx2{l2[0], l2[1]});
+        if (FULL) store_piece(rl[2], v2, rowoff(2, (grpw << 6) + 16 * qg) * 4, floatx2{l2[0], l2[1]});
+        else store_piece_if(rl[2], qok && b2 >= 0, (rowoff(2, rr) + b2) * 4, floatx2{l2[0], l2[1]});
         if (L < 4 || tc.band) continue;
         // level 3 (regular tiles): pixel kb >> 1 of the tile's 1 x 2 from the 2 x 2 level-2 pixels of
         // lanes kb (row 0, kb even) and kb + 1 (row 1), brought over by a row swap; lane kb = 0 takes
@@ -871,47 +631,24 @@ __device__ __forceinline__ void split16_epilogue(const BuildParams& P, floatx4 (
         const auto o1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(l2[1]), __float_as_uint(l2[1]), false, false);
         const float p3 = pool4(l2[0], l2[1], __uint_as_float(o0[1]), __uint_as_float(o1[1]));
         const auto p3s = __builtin_amdgcn_permlane32_swap(__float_as_uint(p3), __float_as_uint(p3), false, false);
-        if (FULL) fst2(r3, v3, rowoff(3, (grpw << 6) + 16 * qg) * 4, floatx2{p3, __uint_as_float(p3s[1])});
-        else st2(r3, (rowoff(3, rr) + b3) * 4, qok && b3 >= 0, floatx2{p3, __uint_as_float(p3s[1])});
+        if (FULL) store_piece(rl[3], v3, rowoff(3, (grpw << 6) + 16 * qg) * 4, floatx2{p3, __uint_as_float(p3s[1])});
+        else store_piece_if(rl[3], qok && b3 >= 0, (rowoff(3, rr) + b3) * 4, floatx2{p3, __uint_as_float(p3s[1])});
     }
 }
 
 template <bool MUL>
 __global__ __launch_bounds__(256, 2) void build_split16_kernel(BuildParams P) {
-    // ALL LDS in this one array (cdna_hip_programming.md trap 4(a), see build_split_kernel)
-    __shared__ __attribute__((aligned(16))) char smem[SLDS + (SQ + 256) * 4];
-    int* exq = reinterpret_cast<int*>(smem + SLDS);   // exponents of the 256 queries
-    int* ext = exq + SQ;                              // ... negated, of the 128 panel targets
-    float* fst = reinterpret_cast<float*>(ext + 128);  // 2^ext when |ext| <= 63
+    __shared__ __attribute__((aligned(16))) char smem[TILE_LDS];   // ALL its LDS (build_tile.h)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b, qt, nt;
-    decode_tile<kGM16, true>(P, xcd_remap(blockIdx.x, gridDim.x), P.n_qt, b, qt, nt);
-    const NTile tc = ntile_of(P, nt);
+    const NTile tc = block_tile<kGM16, true>(P, P.n_qt, b, qt, nt);
     const int q0 = qt * SQ;
-    const int H = P.H, W = P.W;
-    const int64_t Q = (int64_t)H * W;
-
-    // per-pixel exponents: loaded behind the K loop's last static wait (only the epilogue reads them)
-    int eq = 0, et = 0;
-    auto load_exponents = [&]() {
-        eq = q0 + tid < P.q_count ? P.ex1[(int64_t)b * P.q_count + q0 + tid] : 0;
-        if (tid < 128) {
-            int y, x;
-            split16_target(tid, tc.band, y, x);
-            y += tc.ty0;
-            x += tc.tx0;
-            et = (y < H && x < W) ? P.ex2[(int64_t)b * Q + (int64_t)y * W + x] : 0;   // negated after the loop
-        }
-    };
+    int eq = 0, et = 0;   // per-pixel exponents: loaded behind the K loop's last static wait
 
     const int64_t pstride = (int64_t)NCP * PANEL16;   // bytes of one 128-pixel tile's panels
-    const int qp = 2 * qt;
-    const int nqp = min(2, P.n_mt - qp);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(P.pk1 + ((int64_t)b * P.n_mt + qp) * pstride), 0, (int)(nqp * pstride), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(P.pk2 + ((int64_t)b * P.n_nt + nt) * pstride), 0, (int)pstride, 0x00020000);
+    __amdgpu_buffer_rsrc_t rq, rt;
+    panel_rsrc(P, pstride, b, qt, nt, rq, rt);
     // target panel of pair cp: DMA piece c = wave + 4 s of its 16 KB (lane-linear); the pair and
     // piece offsets ride in the scalar soffset, so one VGPR addresses every piece of the loop
     const int tvo = wave * 1024 + lane * 16;
@@ -924,14 +661,7 @@ __global__ __launch_bounds__(256, 2) void build_split16_kernel(BuildParams P) {
     };
 
     floatx4 acc[4][8];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc[g][t] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(acc[g][t]));
+    zero_acc<false>(acc);   // in VGPRs (see mfma below)
 
     // query fragments of the wave's 4 groups (panel wave / 2, 16-query groups 4 (wave & 1) + g), one pair
     struct QF { halfx8 h[4], l[4]; };
@@ -1000,7 +730,7 @@ __global__ __launch_bounds__(256, 2) void build_split16_kernel(BuildParams P) {
                 __builtin_amdgcn_s_barrier();
                 PHASE;
                 if (cp + S16NB - 1 < NCP) issue(cp + S16NB - 1);
-                if (cp + 2 == NCP) load_exponents();   // after the last static wait
+                if (cp + 2 == NCP) load_exponents<split16_target>(P, tc, b, q0, tid, eq, et);   // after the last static wait
                 PHASE;
             }
             if (tg + 1 < 8) read_a(cp, tg + 1, af[(tg + 1) & 1]);
@@ -1016,21 +746,14 @@ __global__ __launch_bounds__(256, 2) void build_split16_kernel(BuildParams P) {
     asm volatile("s_nop 15");
     asm volatile("s_nop 15");
     wait_vm<0, true>();   // the exponents have landed and this wave's reads are done ...
-    exq[tid] = eq;
-    if (tid < 128) {
-        ext[tid] = -et;
-        fst[tid] = exp2i(max(-63, min(-et, 63)));
-    }
+    publish_exponents(smem, tid, eq, et);
     __syncthreads();      // ... in every wave: the panel buffers are the epilogue's scratch
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(acc[g][t]));
+    pin_acc<false>(acc);
     // FULL: a whole query tile starting a 64-row group (block-uniform)
     if (q0 + SQ <= P.q_count && (((int64_t)b * P.q_count + q0) & (kGroup - 1)) == 0)
-        split16_epilogue<MUL, true>(P, acc, smem + wave * (2 * 64 * S16LS), wave * 64, exq, ext, fst, tc, b, q0, lane);
+        split16_epilogue<MUL, true>(P, acc, smem, smem + wave * (2 * 64 * S16LS), wave * 64, tc, b, q0, lane);
     else
-        split16_epilogue<MUL, false>(P, acc, smem + wave * (2 * 64 * S16LS), wave * 64, exq, ext, fst, tc, b, q0, lane);
+        split16_epilogue<MUL, false>(P, acc, smem, smem + wave * (2 * 64 * S16LS), wave * 64, tc, b, q0, lane);
 }
 
 // ============================================================================================
@@ -1077,10 +800,7 @@ static_assert(f32_vm_after(0, 16) == 36 && f32_vm_after(1, 16) == 18 && f32_vm_a
 template <bool MUL>
 __global__ __launch_bounds__(256, 2) void build_f32_kernel(BuildParams P) {
     constexpr int NK = 16;
-    __shared__ __attribute__((aligned(16))) char smem[SLDS + (SQ + 256) * 4];
-    int* exq = reinterpret_cast<int*>(smem + SLDS);
-    int* ext = exq + SQ;
-    float* fst = reinterpret_cast<float*>(ext + 128);
+    __shared__ __attribute__((aligned(16))) char smem[TILE_LDS];   // ALL its LDS (build_tile.h)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1094,11 +814,7 @@ __global__ __launch_bounds__(256, 2) void build_f32_kernel(BuildParams P) {
     const int H = P.H, W = P.W;
     const int64_t Q = (int64_t)H * W;
     // no operand scaling: zero exponents make split_epilogue's scale 1 / sqrt(D) alone
-    exq[tid] = 0;
-    if (tid < 128) {
-        ext[tid] = 0;
-        fst[tid] = 1.0f;
-    }
+    publish_exponents(smem, tid, 0, 0);
 
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(P.f1 + (int64_t)b * P.D * P.q_count), 0, (int)((int64_t)P.D * P.q_count * 4), 0x00020000);
@@ -1127,16 +843,7 @@ __global__ __launch_bounds__(256, 2) void build_f32_kernel(BuildParams P) {
     };
 
     floatx16 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(acc[i][j]));
+    zero_acc<true>(acc);   // pinned to AGPRs
 
     // query fragments: lane (q, kh) of group i, k-step s = fmap1[16 kc + 2 s + kh][q0 + 64 wave + 32 i + q]
     struct QF { float v[2][8]; };
@@ -1215,11 +922,8 @@ __global__ __launch_bounds__(256, 2) void build_f32_kernel(BuildParams P) {
 #undef PHASE
     wait_vm<0, true>();
     __builtin_amdgcn_s_barrier();   // every wave is done with the chunk buffers (epilogue scratch)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(acc[i][j]));
-    split_epilogue<MUL>(P, acc, smem + wave * (4 * 32 * XS), wave * 64, exq, ext, fst, tc, b, q0, lane);
+    pin_acc<true>(acc);
+    split_epilogue<MUL>(P, acc, smem, smem + wave * (4 * 32 * XS), wave * 64, tc, b, q0, lane);
 }
 
 // Split-mode operand pass: per pixel, ex = 15 - E with max_d |x| = f 2^E, f in [0.5, 1) (so the
@@ -1383,12 +1087,17 @@ __device__ __forceinline__ void pack_body(const T* __restrict__ x, const BuildPa
 // drops a launch boundary (round-1 A/B, profiles/r01_final8/ab_pack.txt).  Surplus x blocks of the
 // shorter pass return at once (block-uniform, before pack_body's barrier).
 // T: the fmaps' element (P.f1 / P.f2 point at elements of T; float: the fp32 entries).
+// x blocks of the fmap2 pass (pack_body<true>): 4 per pair of regular n-tiles, 2 per band tile
+__host__ __device__ __forceinline__ int pack_grid_x(const BuildParams& P) {
+    return 4 * (P.n_reg / P.n_ntx) * ((P.n_ntx + 1) / 2) + 2 * (P.n_nt - P.n_reg);
+}
+
 template <bool L16, typename T = float>
 __global__ __launch_bounds__(256) void pack_both_kernel(BuildParams P) {
     if (blockIdx.z == 0) {
         if ((int)blockIdx.x < 2 * P.n_mt)
             pack_body<false, L16, T>(reinterpret_cast<const T*>(P.f1), P, P.ex1, const_cast<char*>(P.pk1));
-    } else if ((int)blockIdx.x < 4 * (P.n_reg / P.n_ntx) * ((P.n_ntx + 1) / 2) + 2 * (P.n_nt - P.n_reg)) {
+    } else if ((int)blockIdx.x < pack_grid_x(P)) {
         pack_body<true, L16, T>(reinterpret_cast<const T*>(P.f2), P, P.ex2, const_cast<char*>(P.pk2));
     }
 }
@@ -1415,16 +1124,29 @@ constexpr int FSM = (FNBUF * KB * (BM + BN) > MR * CS) ? FNBUF * KB * (BM + BN) 
 template <typename V>
 __device__ __forceinline__ void st_nt(V* p, V v) { __builtin_nontemporal_store(v, p); }
 
-struct TileCoord { int b, m0, ty0, tx0, band; };
+// What the two epilogues below share: 8 consecutive floats of a C-tile row from LDS, and 4
+// consecutive level-2 pixels (r, c .. c + 3) of query image row from the pooled staging
+__device__ __forceinline__ void read_row8(const float* p, float (&v)[8]) {
+    const floatx4 lo = *reinterpret_cast<const floatx4*>(p);
+    const floatx4 hi = *reinterpret_cast<const floatx4*>(p + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
+}
+__device__ __forceinline__ void store_level2_row(const BuildParams& P, int64_t row, int r, int c, const float* src) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float* p = level_px(P, 2, row, r, c + j);
+        if (p) *p = src[j];
+    }
+}
 
 // Epilogue of a regular tile (all threads; contains barriers).  Cs = scaled C-tile rows ([m][n],
-// stride CS, n = ty*16 + tx) of MR of the block's queries starting at mlo.  Level 0: 4 whole tiles
-// per query; pooling: thread (query m, 8 x 8 block blk) reduces in registers 8x8 -> 4x4 -> 2x2 ->
-// 1, each level from the rounded previous one, parks levels 1-3 in LDS, then level 1 leaves as
+// stride CS, n = ty*16 + tx) of MR of the block's queries: query images row0 .. of the pyramid, the
+// first mvalid of them in range.  Level 0: 4 whole tiles per query; pooling: thread (query m,
+// 8 x 8 block blk) reduces in registers 8x8 -> 4x4 -> 2x2 -> 1, each level from the rounded previous one, parks levels 1-3 in LDS, then level 1 leaves as
 // one whole tile per query, level 2 as two 16-byte rows, level 3 as single pixels.
-__device__ __forceinline__ void epilogue(const BuildParams& P, const TileCoord& tc, float* Cs, int tid, int mlo) {
-    const int64_t row0 = (int64_t)tc.b * P.q_count + tc.m0 + mlo;
-    const int mvalid = min(MR, P.q_count - tc.m0 - mlo);
+__device__ __forceinline__ void epilogue(const BuildParams& P, const NTile& tc, float* Cs, int tid, int64_t row0,
+                                         int mvalid) {
     {   // level 0
         const int ntx = P.lntx[0], nty = P.lnty[0];
         const int tr0 = tc.ty0 / kTileH, tc0 = tc.tx0 / kTileW;
@@ -1448,12 +1170,7 @@ __device__ __forceinline__ void epilogue(const BuildParams& P, const TileCoord& 
     if (pooler) {
         float v[8][8];
 #pragma unroll
-        for (int ty = 0; ty < 8; ++ty) {
-            const floatx4 lo = *reinterpret_cast<const floatx4*>(Cs + m * CS + ty * TBW + blk * 8);
-            const floatx4 hi = *reinterpret_cast<const floatx4*>(Cs + m * CS + ty * TBW + blk * 8 + 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { v[ty][j] = lo[j]; v[ty][4 + j] = hi[j]; }
-        }
+        for (int ty = 0; ty < 8; ++ty) read_row8(Cs + m * CS + ty * TBW + blk * 8, v[ty]);
 #pragma unroll
         for (int y = 0; y < 4; ++y)
 #pragma unroll
@@ -1491,14 +1208,7 @@ __device__ __forceinline__ void epilogue(const BuildParams& P, const TileCoord& 
     }
     if (P.fused_levels >= 3 && tid < 2 * MR) {   // level 2: rows ty0/4 + {0,1}, cols tx0/4 .. +3
         const int mm = tid >> 1, y = tid & 1;
-        if (mm < mvalid) {
-            const float* src = S2 + mm * P2S + y * 4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float* p = level_px(P, 2, row0 + mm, tc.ty0 / 4 + y, tc.tx0 / 4 + j);
-                if (p) *p = src[j];
-            }
-        }
+        if (mm < mvalid) store_level2_row(P, row0 + mm, tc.ty0 / 4 + y, tc.tx0 / 4, S2 + mm * P2S + y * 4);
     }
     if (P.fused_levels >= 4 && tid < MR && tid < mvalid) {   // level 3: row ty0/8, cols tx0/8 .. +1
 #pragma unroll
@@ -1513,9 +1223,8 @@ __device__ __forceinline__ void epilogue(const BuildParams& P, const TileCoord& 
 // 4 tiles per query.  Pooling: thread (query m, 4x8 block blk = 0..3) reduces 4x8 -> 2x4 -> 1x2 in
 // registers (the reference's order, from the rounded previous level); level 1 leaves as two 8-float
 // rows of two tiles, level 2 as single pixels.  No level-3 pixel draws on these rows.
-__device__ __forceinline__ void epilogue_band(const BuildParams& P, const TileCoord& tc, float* Cs, int tid, int mlo) {
-    const int64_t row0 = (int64_t)tc.b * P.q_count + tc.m0 + mlo;
-    const int mvalid = min(MR, P.q_count - tc.m0 - mlo);
+__device__ __forceinline__ void epilogue_band(const BuildParams& P, const NTile& tc, float* Cs, int tid, int64_t row0,
+                                              int mvalid) {
     {   // level 0: tile row ty0/4, tile cols tx0/8 .. +3
         const int ntx = P.lntx[0];
         const int tr = tc.ty0 / kTileH, tc0 = tc.tx0 / kTileW;
@@ -1539,12 +1248,7 @@ __device__ __forceinline__ void epilogue_band(const BuildParams& P, const TileCo
         if (it < 4 * MR) {
             float v[4][8];
 #pragma unroll
-            for (int ty = 0; ty < 4; ++ty) {
-                const floatx4 lo = *reinterpret_cast<const floatx4*>(Cs + m * CS + ty * 32 + blk * 8);
-                const floatx4 hi = *reinterpret_cast<const floatx4*>(Cs + m * CS + ty * 32 + blk * 8 + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { v[ty][j] = lo[j]; v[ty][4 + j] = hi[j]; }
-            }
+            for (int ty = 0; ty < 4; ++ty) read_row8(Cs + m * CS + ty * 32 + blk * 8, v[ty]);
 #pragma unroll
             for (int y = 0; y < 2; ++y)
 #pragma unroll
@@ -1583,14 +1287,7 @@ __device__ __forceinline__ void epilogue_band(const BuildParams& P, const TileCo
     }
     if (P.fused_levels >= 3 && tid < 2 * MR) {   // level 2: row ty0/4, cols tx0/4 .. +7
         const int mm = tid >> 1, hf = tid & 1;
-        if (mm < mvalid) {
-            const float* src = S2 + mm * P2S + hf * 4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float* p = level_px(P, 2, row0 + mm, tc.ty0 / 4, tc.tx0 / 4 + hf * 4 + j);
-                if (p) *p = src[j];
-            }
-        }
+        if (mm < mvalid) store_level2_row(P, row0 + mm, tc.ty0 / 4, tc.tx0 / 4 + hf * 4, S2 + mm * P2S + hf * 4);
     }
 }
 
@@ -1609,22 +1306,15 @@ __global__ __launch_bounds__(NT, 3) void build_kernel(BuildParams P) {
     float* Bs = smem + NBUF * KB * AS;      // [NBUF][KB][BSS]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    TileCoord tc;
-    {
-        int mt, nt;
-        decode_tile<8, false>(P, xcd_remap(blockIdx.x, gridDim.x), P.n_mt, tc.b, mt, nt);
-        const NTile n = ntile_of(P, nt);
-        tc.m0 = mt * BM;
-        tc.ty0 = n.ty0;
-        tc.tx0 = n.tx0;
-        tc.band = n.band;
-    }
+    int b, mt, nt;
+    const NTile tc = block_tile<8, false>(P, P.n_mt, b, mt, nt);
+    const int m0 = mt * BM;
     const int q_end = P.q_count;
     const int H = P.H, W = P.W, D = P.D;
     const int64_t Q = (int64_t)H * W;
     const int64_t QA = P.q_count;
-    const float* __restrict__ A = P.f1 + (int64_t)tc.b * D * QA;
-    const float* __restrict__ Bm = P.f2 + (int64_t)tc.b * D * Q;
+    const float* __restrict__ A = P.f1 + (int64_t)b * D * QA;
+    const float* __restrict__ Bm = P.f2 + (int64_t)b * D * Q;
 
     floatx4 ra[NLD], rb[NLD];
     auto load_chunk = [&](int k0) {
@@ -1633,7 +1323,7 @@ __global__ __launch_bounds__(NT, 3) void build_kernel(BuildParams P) {
             const int s = tid + NT * i;
             const int k = k0 + (s >> 5);
             {   // A: row k, queries m0 + 4c .. +3
-                const int m = tc.m0 + 4 * (s & 31);
+                const int m = m0 + 4 * (s & 31);
                 floatx4 v = {0.f, 0.f, 0.f, 0.f};
                 if (VEC) {
                     if (k < D && m < q_end) v = *reinterpret_cast<const floatx4*>(A + (int64_t)k * QA + m);
@@ -1705,9 +1395,8 @@ __global__ __launch_bounds__(NT, 3) void build_kernel(BuildParams P) {
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)((int64_t)D * QA * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rsb =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Bm), 0, (int)((int64_t)D * Q * 4), 0x00020000);
-        constexpr int OOB = 0x7ffffff0;   // beyond any operand: reads (and lands in LDS) as 0
         const int c = lane & 31, kl = lane >> 5;
-        const int m = tc.m0 + 4 * c;
+        const int m = m0 + 4 * c;
         const int y = tc.ty0 + (tc.band ? c >> 3 : c >> 2), x = tc.tx0 + 4 * (tc.band ? c & 7 : c & 3);
         const bool aok = m < q_end, bok = y < H && x < W;
         const int abase = m * 4, bbase = (y * W + x) * 4;
@@ -1720,10 +1409,10 @@ __global__ __launch_bounds__(NT, 3) void build_kernel(BuildParams P) {
                 const bool kin = k < D;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rsa, (__attribute__((address_space(3))) void*)(As + (buf * KB + kk) * AS), 16,
-                    aok && kin ? abase + k * (int)QA * 4 : OOB, 0, 0, 0);
+                    aok && kin ? abase + k * (int)QA * 4 : SOOB, 0, 0, 0);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rsb, (__attribute__((address_space(3))) void*)(Bs + (buf * KB + kk) * BSS), 16,
-                    bok && kin ? bbase + k * (int)Q * 4 : OOB, 0, 0, 0);
+                    bok && kin ? bbase + k * (int)Q * 4 : SOOB, 0, 0, 0);
             }
         };
         for (int kc = 0; kc < NBUF - 1 && kc < nk; ++kc) issue(kc);
@@ -1775,8 +1464,11 @@ __global__ __launch_bounds__(NT, 3) void build_kernel(BuildParams P) {
             else write_c([&](float v) { return __fdiv_rn(v, P.scale); });
         }
         __syncthreads();
-        if (tc.band) epilogue_band(P, tc, Cs, tid, half * MR);
-        else epilogue(P, tc, Cs, tid, half * MR);
+        // this half's query images and how many of them are in range
+        const int64_t row0 = (int64_t)b * P.q_count + m0 + half * MR;
+        const int mvalid = min(MR, P.q_count - m0 - half * MR);
+        if (tc.band) epilogue_band(P, tc, Cs, tid, row0, mvalid);
+        else epilogue(P, tc, Cs, tid, row0, mvalid);
         if (half == 0) __syncthreads();   // half 0 fully consumed before half 1 overwrites Cs
     }
 }
@@ -1844,6 +1536,17 @@ void launch_pack(const BuildParams& P, int nx, int B, bool s16, hipStream_t stre
     if (s16) hipLaunchKernelGGL((pack_both_kernel<true, T>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
     else hipLaunchKernelGGL((pack_both_kernel<false, T>), dim3((unsigned)nx, B, 2), dim3(256), 0, stream, P);
 }
+
+// a 256 x 128 kernel's instantiation for the scale mode: mul<true> / div<false>
+void launch_mul(const BuildParams& P, int64_t ntiles, hipStream_t stream, void (*mul)(BuildParams),
+                void (*div)(BuildParams)) {
+    hipLaunchKernelGGL(P.scale_is_mul ? mul : div, dim3((unsigned)ntiles), dim3(256), 0, stream, P);
+}
+
+// both fp32 operands' byte offsets fit the 31-bit buffer range
+bool fits_buffer_range(const BuildParams& P) {
+    return (int64_t)P.D * P.H * P.W * 4 < 0x7fff0000LL && (int64_t)P.D * P.q_count * 4 < 0x7fff0000LL;
+}
 }  // namespace
 
 int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid, hipStream_t stream, int stages,
@@ -1868,8 +1571,7 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
         P.ex2 = reinterpret_cast<int*>(P.ws + w.ex2);
         P.pk1 = P.ws + w.pk1;
         P.pk2 = P.ws + w.pk2;
-        const int nx2 = 4 * (P.n_reg / P.n_ntx) * ((P.n_ntx + 1) / 2) + 2 * (P.n_nt - P.n_reg);   // fmap2 blocks
-        const int nx = 2 * P.n_mt > nx2 ? 2 * P.n_mt : nx2;
+        const int nx = 2 * P.n_mt > pack_grid_x(P) ? 2 * P.n_mt : pack_grid_x(P);
         // D = 256: build_split16_kernel and its panel layout; other D: build_split_kernel
         const bool s16 = (P.D + 15) / 16 == 2 * NCP;
         if (stages & 1) {
@@ -1878,30 +1580,21 @@ int launch_build(const BuildParams& P0, int B, const PyrGeom& g, float* pyramid,
             else launch_pack<float>(P, nx, B, s16, stream);
         }
         if (!(stages & 2)) return hip_status();
-        const dim3 grid((unsigned)ntiles);
-        if (s16) {
-            if (P.scale_is_mul) hipLaunchKernelGGL((build_split16_kernel<true>), grid, dim3(256), 0, stream, P);
-            else hipLaunchKernelGGL((build_split16_kernel<false>), grid, dim3(256), 0, stream, P);
-        } else {
-            if (P.scale_is_mul) hipLaunchKernelGGL((build_split_kernel<true>), grid, dim3(256), 0, stream, P);
-            else hipLaunchKernelGGL((build_split_kernel<false>), grid, dim3(256), 0, stream, P);
-        }
+        if (s16) launch_mul(P, ntiles, stream, build_split16_kernel<true>, build_split16_kernel<false>);
+        else launch_mul(P, ntiles, stream, build_split_kernel<true>, build_split_kernel<false>);
     } else {
         // D = 256 with 4-aligned rows and 31-bit operand offsets: the 256 x 128 fp32 kernel
-        if (P.D == 256 && P.W % 4 == 0 && (uintptr_t)P.f2 % 16 == 0 && (int64_t)P.D * P.H * P.W * 4 < 0x7fff0000LL &&
-            (int64_t)P.D * P.q_count * 4 < 0x7fff0000LL) {
+        if (P.D == 256 && P.W % 4 == 0 && (uintptr_t)P.f2 % 16 == 0 && fits_buffer_range(P)) {
             const int64_t nt2 = (int64_t)B * P.n_qt * P.n_nt;
             if (nt2 <= 0 || nt2 > 0x7fffffff) return ECORR_EINVAL;
-            if (P.scale_is_mul) hipLaunchKernelGGL((build_f32_kernel<true>), dim3((unsigned)nt2), dim3(256), 0, stream, P);
-            else hipLaunchKernelGGL((build_f32_kernel<false>), dim3((unsigned)nt2), dim3(256), 0, stream, P);
+            launch_mul(P, nt2, stream, build_f32_kernel<true>, build_f32_kernel<false>);
         } else {   // any D: the 128 x 128 fp32 kernel
             const int64_t ntiles = (int64_t)B * P.n_mt * P.n_nt;
             if (ntiles <= 0 || ntiles > 0x7fffffff) return ECORR_EINVAL;
             const bool vec = (P.W % 4 == 0) && (P.q_count % 4 == 0) && ((uintptr_t)P.f1 % 16 == 0) &&
                              ((uintptr_t)P.f2 % 16 == 0);
             // LDS-DMA staging whenever both operands' byte offsets fit the 31-bit buffer range
-            const bool glds = vec && (int64_t)P.D * P.H * P.W * 4 < 0x7fff0000LL &&
-                              (int64_t)P.D * P.q_count * 4 < 0x7fff0000LL;
+            const bool glds = vec && fits_buffer_range(P);
             const dim3 grid((unsigned)ntiles), block(NT);
             if (glds) hipLaunchKernelGGL((build_kernel<true, true>), grid, block, 0, stream, P);
             else if (vec) hipLaunchKernelGGL((build_kernel<true, false>), grid, block, 0, stream, P);

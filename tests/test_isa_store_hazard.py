@@ -81,12 +81,11 @@ def compiled():
         bad = os.path.join(d, "e-raft_amd", "csrc")   # the tree's layout: the sources include ../../include
         shutil.copytree(CSRC, bad, ignore=shutil.ignore_patterns("build"))
         shutil.copytree(os.path.join(ROOT, "include"), os.path.join(d, "include"))
-        p = os.path.join(bad, "build.hip")
-        s = open(p).read()
-        for _, old, new in lab_build.PATCHES["soff_full"]:
+        for fname, old, new in lab_build.PATCHES["soff_full"]:   # each patch in the file it names
+            p = os.path.join(bad, fname)
+            s = open(p).read()
             assert old in s
-            s = s.replace(old, new)
-        open(p, "w").write(s)
+            open(p, "w").write(s.replace(old, new))
         with concurrent.futures.ThreadPoolExecutor(8) as ex:
             jobs = {n: ex.submit(_asm, CSRC, n, d) for n in SOURCES}
             jobs["soff_full"] = ex.submit(_asm, bad, "build", bad)

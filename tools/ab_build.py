@@ -97,8 +97,11 @@ def main():
                     times[name].append(e0.elapsed_time(e1) / 5)
             for name, ts in times.items():
                 med = statistics.median(ts)
-                print(f"build {B}x{D}x{H}x{W} {name:5s} median {med * 1e3:.1f} us  min {min(ts) * 1e3:.1f}", flush=True)
+                q1, _, q3 = statistics.quantiles(ts, n=4) if len(ts) > 1 else (med, med, med)
+                print(f"build {B}x{D}x{H}x{W} {name:5s} median {med * 1e3:.1f} us  min {min(ts) * 1e3:.1f}"
+                      f"  q1 {q1 * 1e3:.1f}  q3 {q3 * 1e3:.1f}", flush=True)
                 res[f"{B}x{D}x{H}x{W}/{name}"] = round(med * 1e3, 1)
+                res[f"{B}x{D}x{H}x{W}/{name}/iqr"] = round((q3 - q1) * 1e3, 1)
         print(json.dumps({"ab_build_us": res, "mode": MODE}))
 
 

@@ -31,7 +31,7 @@ PATCHES = {
 """)],
 }
 # epilogue pieces: level 0 only (scaling + LDS line transposes + stores); no level-2/3 pixel stores
-PATCHES["l0only"] = [("build.hip", "    const int L = P.fused_levels;\n    const int64_t rows0", "    const int L = 1;\n    const int64_t rows0")]
+PATCHES["l0only"] = [("build.hip", "    const int L = P.fused_levels;\n    // per-level descriptors", "    const int L = 1;\n    // per-level descriptors")]
 PATCHES["prio"] = [("build.hip", "    // ---------------- epilogue (per wave, from registers) ----------------\n",
                      "    // ---------------- epilogue (per wave, from registers) ----------------\n    __builtin_amdgcn_s_setprio(2);\n")]
 PATCHES["prio3"] = [("build.hip", "    // ---------------- epilogue (per wave, from registers) ----------------\n",
@@ -79,27 +79,15 @@ extern "C" __attribute__((visibility("default"))) int ecorr_lab_stamps16(void* d
 }
 """
 PATCHES["st16"] = [
-    ("build.hip", "constexpr int SQ = 256; ", ST16_DECL + "constexpr int SQ = 256; "),
+    ("build_tile.h", "constexpr int SQ = 256; ", ST16_DECL + "constexpr int SQ = 256; "),
     ("build.hip", """    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b, qt, nt;
-    decode_tile<kGM16, true>(P, xcd_remap(blockIdx.x, gridDim.x), P.n_qt, b, qt, nt);
-    const NTile tc = ntile_of(P, nt);
-    const int q0 = qt * SQ;
-    const int H = P.H, W = P.W;
-    const int64_t Q = (int64_t)H * W;
-
-    // per-pixel exponents: loaded behind the K loop's last static wait (only the epilogue reads them)""",
+    const NTile tc = block_tile<kGM16, true>(P, P.n_qt, b, qt, nt);""",
      """    const unsigned long long r_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long c_mid = 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b, qt, nt;
-    decode_tile<kGM16, true>(P, xcd_remap(blockIdx.x, gridDim.x), P.n_qt, b, qt, nt);
-    const NTile tc = ntile_of(P, nt);
-    const int q0 = qt * SQ;
-    const int H = P.H, W = P.W;
-    const int64_t Q = (int64_t)H * W;
-
-    // per-pixel exponents: loaded behind the K loop's last static wait (only the epilogue reads them)"""),
+    const NTile tc = block_tile<kGM16, true>(P, P.n_qt, b, qt, nt);"""),
     ("build.hip", """    wait_vm_n<true>(s16_vm_after(0));   // t(0) landed
     __builtin_amdgcn_s_barrier();
     PHASE;""", """    wait_vm_n<true>(s16_vm_after(0));   // t(0) landed
@@ -119,8 +107,8 @@ PATCHES["st16"] = [
     ("build.hip", """    __syncthreads();      // ... in every wave: the panel buffers are the epilogue's scratch""",
      """    __syncthreads();      // ... in every wave: the panel buffers are the epilogue's scratch
     const unsigned long long c_loop1 = __builtin_amdgcn_s_memtime(), r_loop1 = __builtin_amdgcn_s_memrealtime();"""),
-    ("build.hip", """        split16_epilogue<MUL, false>(P, acc, smem + wave * (2 * 64 * S16LS), wave * 64, exq, ext, fst, tc, b, q0, lane);
-}""", """        split16_epilogue<MUL, false>(P, acc, smem + wave * (2 * 64 * S16LS), wave * 64, exq, ext, fst, tc, b, q0, lane);
+    ("build.hip", """        split16_epilogue<MUL, false>(P, acc, smem, smem + wave * (2 * 64 * S16LS), wave * 64, tc, b, q0, lane);
+}""", """        split16_epilogue<MUL, false>(P, acc, smem, smem + wave * (2 * 64 * S16LS), wave * 64, tc, b, q0, lane);
     __syncthreads();
     if (tid == 0 && blockIdx.x < 65536) {
         unsigned long long* g = g_st16[blockIdx.x];
@@ -154,10 +142,8 @@ PATCHES["prio_epi"] = [("build.hip", """    wait_vm<0, true>();   // the exponen
      """    __builtin_amdgcn_s_setprio(1);
     wait_vm<0, true>();   // the exponents have landed and this wave's reads are done ...""")]
 PATCHES["onecu16"] = [("build.hip", """__global__ __launch_bounds__(256, 2) void build_split16_kernel(BuildParams P) {
-    // ALL LDS in this one array (cdna_hip_programming.md trap 4(a), see build_split_kernel)
-    __shared__ __attribute__((aligned(16))) char smem[SLDS + (SQ + 256) * 4];""", """__global__ __launch_bounds__(256, 1) void build_split16_kernel(BuildParams P) {
-    // ALL LDS in this one array (cdna_hip_programming.md trap 4(a), see build_split_kernel)
-    __shared__ __attribute__((aligned(16))) char smem[SLDS + (SQ + 256) * 4 + 16384];""")]
+    __shared__ __attribute__((aligned(16))) char smem[TILE_LDS];""", """__global__ __launch_bounds__(256, 1) void build_split16_kernel(BuildParams P) {
+    __shared__ __attribute__((aligned(16))) char smem[TILE_LDS + 16384];""")]
 # (round 3: split16 level-0 lines stored straight from their lanes, no LDS transpose -- the source
 # option is gone: 4.8 ms and 5.4 GB written, profiles/r03_lab/r3h_*)
 # the query-stationary persistent build (build_qs_kernel) in place of build_split16_kernel
@@ -176,7 +162,7 @@ PATCHES["qsnomfst0"] = PATCHES["qsnomf"] + PATCHES["qsst0"][1:]
 PATCHES["qsnowait"] = PATCHES["qs"] + [("build.hip", "    using WN = std::integral_constant<int, QS_NST>;",
                                         "    using WN = std::integral_constant<int, 63>;")]
 # split16 level-0/1 stores as nt | sc1 instead of nt
-PATCHES["st18"] = [("build.hip", "constexpr int ST_L01 = 2; ", "constexpr int ST_L01 = 18;")]
+PATCHES["st18"] = [("build_tile.h", "constexpr int ST_L01 = 2; ", "constexpr int ST_L01 = 18;")]
 # QS scheduling freedom: no scheduling barrier between the interleaved steps / one per two steps
 PATCHES["qsnosb"] = PATCHES["qs"] + [("build.hip", "            if constexpr (EPI) epi_step(AE, kc, fast_c);\n            __builtin_amdgcn_sched_barrier(0);",
                                       "            if constexpr (EPI) epi_step(AE, kc, fast_c);")]
@@ -216,7 +202,8 @@ PATCHES["mo_nolookup_nomfma"] = PATCHES["mo_nolookup"] + [("motion.hip", """    
 PATCHES["mo_nolookup_nomfma_nost"] = PATCHES["mo_nolookup_nomfma"] + [("motion.hip", "                        out[((int64_t)b * O + o) * P.q_count + q] = v < 0.0f ? 0.0f : v;   // NaN stays NaN",
     "                        if (v == 1234.5f) out[((int64_t)b * O + o) * P.q_count + q] = v;")]
 PATCHES["mo_nolookup_nost"] = PATCHES["mo_nolookup"] + PATCHES["mo_nolookup_nomfma_nost"][-1:]
-PATCHES["l01oob"] = [("build.hip", "ok ? base + (int)(s * lsz * 4) : SOOB, 0, ST_L01);", "ok ? SOOB : SOOB, 0, ST_L01);")]
+_L01_ST = "        for (int s = 0; s < 4; ++s) store_piece_if(rs, ok, base + (int)(s * lsz * 4), pc[s]);\n"
+PATCHES["l01oob"] = [("build.hip", _L01_ST, _L01_ST.replace("(rs, ok, ", "(rs, false, "))]
 PATCHES["dmaoob"] = [("build.hip", "in ? kc * PANEL + c * 1024 + lane * 16 : SOOB, 0, 0, 0);", "in ? SOOB : SOOB, 0, 0, 0);")]
 PATCHES["qoob"] = [("build.hip", "rq, in ? qgo + kc * PANEL + i * 2048 : SOOB, 0, 0));", "rq, in ? SOOB : SOOB, 0, 0));"),
                    ("build.hip", "rq, in ? qgo + kc * PANEL + i * 2048 + 1024 : SOOB, 0, 0));", "rq, in ? SOOB : SOOB, 0, 0));")]
@@ -224,20 +211,19 @@ PATCHES["qoob"] = [("build.hip", "rq, in ? qgo + kc * PANEL + i * 2048 : SOOB, 0
 for _dt in (3, 5, 6):
     PATCHES[f"dt{_dt}"] = [("build.hip", "constexpr int SNBUF = 4; ", f"constexpr int SNBUF = {_dt}; ")]
 # timing only: every block reads the same query / target panels (all L2 hits, same traffic to the CUs)
-PATCHES["sameq"] = [("build.hip", "P.pk1 + ((int64_t)b * P.n_mt + qp) * pstride", "P.pk1")]
-PATCHES["samet"] = [("build.hip", "P.pk2 + ((int64_t)b * P.n_nt + nt) * pstride", "P.pk2")]
+PATCHES["sameq"] = [("build_tile.h", "P.pk1 + ((int64_t)b * P.n_mt + qp) * pstride", "P.pk1")]
+PATCHES["samet"] = [("build_tile.h", "P.pk2 + ((int64_t)b * P.n_nt + nt) * pstride", "P.pk2")]
 # epilogue pacing: s_sleep after each level-0 line's four stores (timing A/B; bitwise the same)
 for _sl in (2, 6, 16):
-    PATCHES[f"pace{_sl}"] = [("build.hip", "ok ? base + (int)(s * lsz * 4) : SOOB, 0, ST_L01);\n",
-                              f"ok ? base + (int)(s * lsz * 4) : SOOB, 0, ST_L01);\n        __builtin_amdgcn_s_sleep({_sl});\n")]
+    PATCHES[f"pace{_sl}"] = [("build.hip", _L01_ST, _L01_ST + f"        __builtin_amdgcn_s_sleep({_sl});\n")]
 COMBOS = {}
 COMBOS.update({"sameqt": ["sameq", "samet"]})
 # round 6, timing only: the store stream kept, every panel AND per-pixel exponent
 # read from batch item 0's first tiles (L2-resident), so the K loop's reads never leave the L2
-PATCHES["sameex"] = [("build.hip", "eq = q0 + tid < P.q_count ? P.ex1[(int64_t)b * P.q_count + q0 + tid] : 0;",
+PATCHES["sameex"] = [("build_tile.h", "eq = q0 + tid < P.q_count ? P.ex1[(int64_t)b * P.q_count + q0 + tid] : 0;",
                       "eq = q0 + tid < P.q_count ? P.ex1[tid] : 0;"),
-                     ("build.hip", "et = (y < H && x < W) ? P.ex2[(int64_t)b * Q + (int64_t)y * W + x] : 0;",
-                      "et = (y < H && x < W) ? P.ex2[tid] : 0;")]
+                     ("build_tile.h", "et = (y < P.H && x < P.W) ? P.ex2[b * ((int64_t)P.H * P.W) + (int64_t)y * P.W + x] : 0;",
+                      "et = (y < P.H && x < P.W) ? P.ex2[tid] : 0;")]
 COMBOS.update({"l2rd": ["sameq", "samet", "sameex"]})
 # round 6, timing only: the level-0 stores of FULL tiles into one contiguous 128-KB region per block
 # (l0contig: a wave's 8 stores of a query group fill 8 KB; l0c1k: each store instruction writes 1 KB
@@ -247,12 +233,12 @@ _L0C_DECL = ("build.hip", "    const int grpw = qwu >> 6;   // FULL: the wave's 
              "    const int grpw = qwu >> 6;   // FULL: the wave's interleaved group (block-relative)\n"
              "    const __amdgpu_buffer_rsrc_t r0c = __builtin_amdgcn_make_buffer_rsrc(P.lvl[0], 0, 0x7ffffff0, 0x00020000);\n"
              "    const int c0 = (int)(blockIdx.x * 131072u) + (qwu >> 6) * 4 * 8192 + L0C_LANE;\n")
-PATCHES["l0contig"] = [("build.hip", "constexpr int SQ = 256; ", "#define L0C_LANE ((8 * jl) * 128 + 16 * pc)\nconstexpr int SQ = 256; "), _L0C_DECL,
-                       ("build.hip", "            if (FULL) fst4(r0, v0, (qwu + 16 * qg + s) * l0stride, x);",
-                        "            if (FULL) fst4(r0c, c0 + qg * 8192 + s * 128, 0, x);")]
-PATCHES["l0c1k"] = [("build.hip", "constexpr int SQ = 256; ", "#define L0C_LANE (jl * 128 + 16 * pc)\nconstexpr int SQ = 256; "), _L0C_DECL,
-                    ("build.hip", "            if (FULL) fst4(r0, v0, (qwu + 16 * qg + s) * l0stride, x);",
-                     "            if (FULL) fst4(r0c, c0 + qg * 8192 + s * 1024, 0, x);")]
+PATCHES["l0contig"] = [("build_tile.h", "constexpr int SQ = 256; ", "#define L0C_LANE ((8 * jl) * 128 + 16 * pc)\nconstexpr int SQ = 256; "), _L0C_DECL,
+                       ("build.hip", "            if (FULL) store_piece(rl[0], v0, (qwu + 16 * qg + s) * l0stride, x);",
+                        "            if (FULL) store_piece(r0c, c0 + qg * 8192 + s * 128, 0, x);")]
+PATCHES["l0c1k"] = [("build_tile.h", "constexpr int SQ = 256; ", "#define L0C_LANE (jl * 128 + 16 * pc)\nconstexpr int SQ = 256; "), _L0C_DECL,
+                    ("build.hip", "            if (FULL) store_piece(rl[0], v0, (qwu + 16 * qg + s) * l0stride, x);",
+                     "            if (FULL) store_piece(r0c, c0 + qg * 8192 + s * 1024, 0, x);")]
 COMBOS.update({"dmaqoob": ["dmaoob", "qoob"], "noepi_r2": ["noepi"]})
 COMBOS.update({"st16_prio_loop": ["st16", "prio_loop"]})
 COMBOS.update({"noepi_mfma16": ["noepi", "mfma16"]})
@@ -260,19 +246,17 @@ COMBOS.update({"st16_sscale": ["st16", "sscale"], "st16_noscale": ["st16", "nosc
 # round 6: the round-3 split16 ablations, rebuilt on today's kernel (their recipes were retired; the
 # older noepi / l01oob patch the 32x32 build_split_kernel, not split16): every epilogue store out of
 # range (same instructions, no store traffic), and the epilogue replaced by one store per lane
+# (store_piece is the one store of all three 256 x 128 kernels' epilogues: the split and fp32 kernels'
+# stores go out of range with split16's)
 PATCHES["s16_stoob"] = [
-    ("build.hip", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, ok ? off : SOOB, 0, ST_L01);",
-     "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, (ok ? off : SOOB) | 0x70000000, 0, ST_L01);"),
-    ("build.hip", "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, ok ? off : SOOB, 0, ST_L01);",
-     "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, (ok ? off : SOOB) | 0x70000000, 0, ST_L01);"),
-    ("build.hip", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, voff + uoff, 0, ST_L01);",
+    ("build_tile.h", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, voff + uoff, 0, ST_L01);",
      "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, (voff + uoff) | 0x70000000, 0, ST_L01);"),
-    ("build.hip", "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, ST_L01);",
+    ("build_tile.h", "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, ST_L01);",
      "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, (voff + uoff) | 0x70000000, 0, ST_L01);")]
 PATCHES["s16_noepi"] = [("build.hip", """    if (q0 + SQ <= P.q_count && (((int64_t)b * P.q_count + q0) & (kGroup - 1)) == 0)
-        split16_epilogue<MUL, true>(P, acc, smem + wave * (2 * 64 * S16LS), wave * 64, exq, ext, fst, tc, b, q0, lane);
+        split16_epilogue<MUL, true>(P, acc, smem, smem + wave * (2 * 64 * S16LS), wave * 64, tc, b, q0, lane);
     else
-        split16_epilogue<MUL, false>(P, acc, smem + wave * (2 * 64 * S16LS), wave * 64, exq, ext, fst, tc, b, q0, lane);
+        split16_epilogue<MUL, false>(P, acc, smem, smem + wave * (2 * 64 * S16LS), wave * 64, tc, b, q0, lane);
 }""", """    {
         float s = 0.f;
 #pragma unroll
@@ -290,16 +274,16 @@ COMBOS.update({"st16_s16stoob": ["st16", "s16_stoob"]})
 PATCHES["s16_rd8"] = [("build.hip", """#pragma unroll
         for (int s = 0; s < 8; ++s) {
             const floatx4 x = *reinterpret_cast<const floatx4*>(xr + (s + 8 * jl) * S16LS + 16 * pc);
-            if (FULL) fst4(r0, v0, (qwu + 16 * qg + s) * l0stride, x);
-            else st4(r0, l0off + (16 * qg + s) * l0stride, l0ok && l0q + 16 * qg + s < nq, x);
+            if (FULL) store_piece(rl[0], v0, (qwu + 16 * qg + s) * l0stride, x);
+            else store_piece_if(rl[0], l0ok && l0q + 16 * qg + s < nq, l0off + (16 * qg + s) * l0stride, x);
         }""", """        floatx4 xs8[8];
 #pragma unroll
         for (int s = 0; s < 8; ++s) xs8[s] = *reinterpret_cast<const floatx4*>(xr + (s + 8 * jl) * S16LS + 16 * pc);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            if (FULL) fst4(r0, v0, (qwu + 16 * qg + s) * l0stride, xs8[s]);
-            else st4(r0, l0off + (16 * qg + s) * l0stride, l0ok && l0q + 16 * qg + s < nq, xs8[s]);
+            if (FULL) store_piece(rl[0], v0, (qwu + 16 * qg + s) * l0stride, xs8[s]);
+            else store_piece_if(rl[0], l0ok && l0q + 16 * qg + s < nq, l0off + (16 * qg + s) * l0stride, xs8[s]);
         }""")]
 # round 6, timing only (what bounds the split conv's instruction floor?): the split VALU replaced
 # by one conversion per value (lo = 0), and the A-fragment LDS reads replaced by register values
@@ -352,32 +336,27 @@ PATCHES["cv_mixasm"] = [("split_f16.h", """__device__ __forceinline__ void split
 # register-file traffic with the MFMAs' accumulator reads / writes; the epilogue pays one
 # v_accvgpr_read per accumulator (bitwise the same pyramid)
 PATCHES["s16_agpr"] = [
-    ("build.hip", """        for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(acc[g][t]));
-
-    // query fragments""", """        for (int t = 0; t < 8; ++t) asm volatile("" : "+a"(acc[g][t]));
-
-    // query fragments"""),
+    ("build.hip", "    zero_acc<false>(acc);   // in VGPRs (see mfma below)\n", "    zero_acc<true>(acc);\n"),
     ("build.hip", """asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(bq));""",
      """asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(bq));"""),
-    ("build.hip", """        for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(acc[g][t]));
-    // FULL""", """        for (int t = 0; t < 8; ++t) asm volatile("" : "+a"(acc[g][t]));
-    // FULL""")]
+    ("build.hip", "    pin_acc<false>(acc);\n    // FULL", "    pin_acc<true>(acc);\n    // FULL")]
 
 # ---- round 4: the split16 epilogue's scaling (bitwise-equal variants unless marked timing only)
-_S16_PK = """                for (int h = 0; h < 2; ++h) {
-                    const floatx2 x = floatx2{acc[qg][tg][2 * h], acc[qg][tg][2 * h + 1]} *
-                                      (sq2 * floatx2{s4[2 * h], s4[2 * h + 1]});
-                    v[tg][2 * h] = MUL ? x[0] : __fdiv_rn(x[0], P.scale);
-                    v[tg][2 * h + 1] = MUL ? x[1] : __fdiv_rn(x[1], P.scale);
-                }"""
+# (scale4_fast, build_tile.h, is the fast scale step of all three 256 x 128 kernels: these variants
+# change the split and fp32 kernels' epilogue with split16's)
+_S16_PK = """    for (int h = 0; h < 2; ++h) {
+        const floatx2 x = floatx2{a[2 * h], a[2 * h + 1]} * (sq2 * floatx2{s4[2 * h], s4[2 * h + 1]});
+        v[2 * h] = MUL ? x[0] : __fdiv_rn(x[0], P.scale);
+        v[2 * h + 1] = MUL ? x[1] : __fdiv_rn(x[1], P.scale);
+    }"""
 # scalar v_mul_f32 instead of v_pk_mul_f32 (MI355X_MICROARCH.md: packed f32 VALU beside MFMAs is
 # an anti-lever), same products in the same order
-PATCHES["sscale"] = [("build.hip", _S16_PK, """                for (int t = 0; t < 4; ++t) {
-                    const float x = __fmul_rn(acc[qg][tg][t], __fmul_rn(sq, s4[t]));
-                    v[tg][t] = MUL ? x : __fdiv_rn(x, P.scale);
-                }""")]
+PATCHES["sscale"] = [("build_tile.h", _S16_PK, """    for (int t = 0; t < 4; ++t) {
+        const float x = __fmul_rn(a[t], __fmul_rn(sq2[0], s4[t]));
+        v[t] = MUL ? x : __fdiv_rn(x, P.scale);
+    }""")]
 # timing only: no scaling at all (v = acc): what the scaling costs
-PATCHES["noscale"] = [("build.hip", _S16_PK, """                for (int t = 0; t < 4; ++t) v[tg][t] = acc[qg][tg][t] + s4[t] * 0.0f;""")]
+PATCHES["noscale"] = [("build_tile.h", _S16_PK, """    for (int t = 0; t < 4; ++t) v[t] = a[t] + s4[t] * 0.0f;""")]
 
 
 # ---- round 4: fused lookup + convc1, second resident workgroup of each CU in the first dispatch
@@ -586,9 +565,9 @@ for _a in (1, 16, 17):
 # round 5, VERDICT r4 item 3: the FULL epilogue's wave-uniform store term in the scalar soffset
 # instead of the voffset (the round-3 variant that lost ~0.03% of level-0 stores): tools/soff_repro.py
 PATCHES["soff_full"] = [
-    ("build.hip", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, voff + uoff, 0, ST_L01);",
+    ("build_tile.h", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, voff + uoff, 0, ST_L01);",
      "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rs, voff, uoff, ST_L01);"),
-    ("build.hip", "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, ST_L01);",
+    ("build_tile.h", "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, ST_L01);",
      "__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff, uoff, ST_L01);")]
 
 # round 5: the split16 GEMM's grouped tile order -- GM m-tiles x all n-tiles per group (tree: 8)
@@ -751,20 +730,18 @@ PATCHES["lk_ldnt"] = [("lookup_stage.h", "const uint2v u = __builtin_amdgcn_raw_
 # densely) stored with the default policy (or only level 3), so that they may stay in the Infinity
 # Cache for the lookups; levels 0-1 stay nt.  Step-level A/B: tools/ab_step.py
 def _st23(aux, levels):
-    rep = [("build.hip", """    auto fst2 = [&](__amdgpu_buffer_rsrc_t rs, int voff, int uoff, floatx2 v) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, ST_L01);
-    };""", """    auto fst2 = [&](__amdgpu_buffer_rsrc_t rs, int voff, int uoff, floatx2 v) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, ST_L01);
-    };
-    auto fst2p = [&](__amdgpu_buffer_rsrc_t rs, int voff, int uoff, floatx2 v) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, %d);
-    };
-    auto st2p = [&](__amdgpu_buffer_rsrc_t rs, int off, bool ok, floatx2 v) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, ok ? off : SOOB, 0, %d);
-    };""" % (aux, aux))]
+    tmpl = "// ... at byte off, dropped unless ok (off is computed either way: a select, not a branch)\n"
+    rep = [("build_tile.h", tmpl, """// (lab) the 8-byte piece with cache policy %d
+__device__ __forceinline__ void store_piece_p(__amdgpu_buffer_rsrc_t rs, int voff, int uoff, floatx2 v) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, v), rs, voff + uoff, 0, %d);
+}
+__device__ __forceinline__ void store_piece_p_if(__amdgpu_buffer_rsrc_t rs, bool ok, int off, floatx2 v) {
+    store_piece_p(rs, ok ? off : SOOB, 0, v);
+}
+""" % (aux, aux) + tmpl)]
     for lv in levels:
-        rep += [("build.hip", f"if (FULL) fst2(r{lv}, v{lv},", f"if (FULL) fst2p(r{lv}, v{lv},"),
-                ("build.hip", f"else st2(r{lv}, (rowoff({lv}, rr)", f"else st2p(r{lv}, (rowoff({lv}, rr)")]
+        rep += [("build.hip", f"if (FULL) store_piece(rl[{lv}], v{lv},", f"if (FULL) store_piece_p(rl[{lv}], v{lv},"),
+                ("build.hip", f"else store_piece_if(rl[{lv}], qok && b{lv} >= 0,", f"else store_piece_p_if(rl[{lv}], qok && b{lv} >= 0,")]
     return rep
 PATCHES["st23_plain"] = _st23(0, (2, 3))
 PATCHES["st3_plain"] = _st23(0, (3,))
@@ -825,6 +802,14 @@ RETIRED = {n: "4dc7dd1" for n in (
     "cv_bothoob", "cv_l2ld", "cv_soff", "cv_soff_pf3", "cvq2p1", "cvq4p1", "cvq4p2", "cvt2", "cvt2p3",
     "lkw_bothoob", "lkw_ld1", "lkw_ld16", "lkw_ld17", "lkw_ldoob", "lkw_st1", "lkw_st16", "lkw_st17", "lkw_st19",
     "lkw_st3")}
+# The 16-bit convc1 output (7be4e8f) rewrote conv.hip's and motion.hip's output stores and moved
+# build.hip past lab_patches/build_qs.diff.
+RETIRED.update({n: "7671499" for n in (
+    "cv_stoob", "mo_nolookup_nomfma_nost", "mo_nolookup_nost", "mo_wsst", "qs", "qsnomf", "qsnomfst0", "qsnosb",
+    "qsnost", "qsnowait", "qssb2", "qsst0")})
+# build_tile.h: the scale-mode launch became launch_mul, whose kernels take BuildParams alone; the
+# persistent variant's extra tile-count argument has no place in it.
+RETIRED["s16_pers"] = "5b0c790"
 
 
 def build(name):
