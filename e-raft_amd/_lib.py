@@ -63,6 +63,12 @@ SYMBOLS = {
     "ecorr_build_split_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (B, D, H, W, q_count, levels, pyramid, workspace, stream)
     "ecorr_build_split_gemm": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    # the hi-only split build (added within ABI 17): the size entry, pack_as, gemm and as with a hi
+    # workspace (256 bytes of flag block in front of the split workspace)
+    "ecorr_build_split_hi_workspace_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_build_split_pack_hi_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "ecorr_build_split_gemm_hi": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ecorr_build_split_hi_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # (pyramid, coords, B, H, W, q_count, levels, radius, out, stream)
     "ecorr_lookup": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     # a 16-bit (or fp32) output element (added within ABI 17):
@@ -303,6 +309,30 @@ stage_event = None   # bench.py: the timing-event class for stage_events (defaul
 stage_event_start = True
 
 
+# Whether the split build of float16 / bfloat16 fmaps takes the hi-only entries
+# (ecorr_build_split_pack_hi_as / ecorr_build_split_gemm_hi: one MFMA per product while every lo half is
+# +-0, which finite 16-bit fmaps guarantee; bitwise the pyramid of the plain entries either way).
+# On by default: at DSEC size the build is 14-16% shorter at B = 16 and 10-14% at B = 4, beyond the
+# plain arm's spread in every run of profiles/hi_build/bench_hi_build.json.  ECORR_BUILD_HI = 0 | 1 overrides the default;
+# fp32 fmaps never take the hi entries.
+BUILD_HI_DEFAULT = "1"
+_build_hi = os.environ.get("ECORR_BUILD_HI", BUILD_HI_DEFAULT)
+if _build_hi not in ("0", "1"):
+    raise ValueError(f"ECORR_BUILD_HI={_build_hi!r} not in ('0', '1')")
+_build_hi = _build_hi == "1"
+
+
+def set_build_hi(on: bool):
+    global _build_hi
+    if not isinstance(on, (bool, int)) or on not in (0, 1):
+        raise ValueError(f"build_hi {on!r}: expected a bool")
+    _build_hi = bool(on)
+
+
+def build_hi() -> bool:
+    return _build_hi
+
+
 def set_build_mode(mode: str):
     global _build_mode
     if mode not in BUILD_MODES:
@@ -320,14 +350,17 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
     size) is a temporary from the caching allocator, released stream-ordered after the launch.
     float16 / bfloat16 fmaps (both of one dtype, checked by the caller): the split build's operand pass
     reads them as they are (ecorr_build_split_pack_as: bitwise the pack of their .float()); the fp32
-    build has no 16-bit input and gets .float() temporaries."""
+    build has no 16-bit input and gets .float() temporaries.  With build_hi() they take the hi-only
+    entries instead: the same pyramid bit for bit, the GEMM on one MFMA per product."""
     mode = mode or _build_mode
     if mode not in BUILD_MODES:
         raise ValueError(f"build mode {mode!r} not in {BUILD_MODES}")
     pyr = torch.empty(off[-1], dtype=torch.float32, device=fmap2.device)
     st = stream_of(fmap2)
     if mode == "split":
-        ws = scratch("ecorr_build_split_workspace_size", B, D, H, W, q_count, device=fmap2.device, what=what)
+        hi = _build_hi and fmap1.dtype != torch.float32
+        ws = scratch("ecorr_build_split_hi_workspace_size" if hi else "ecorr_build_split_workspace_size",
+                     B, D, H, W, q_count, device=fmap2.device, what=what)
         tm = stage_events
         if tm is not None:   # bench.py: HIP events on this stream around the two stages
             mk = stage_event or (lambda: torch.cuda.Event(enable_timing=True))
@@ -338,12 +371,13 @@ def build_pyramid(fmap1, fmap2, B, D, H, W, q_count, levels, off, what, mode=Non
             check(lib().ecorr_build_split_pack(fmap1.data_ptr(), fmap2.data_ptr(), B, D, H, W, q_count,
                                                ws.data_ptr(), st), what)
         else:
-            check(lib().ecorr_build_split_pack_as(fmap1.data_ptr(), fmap2.data_ptr(), ELEM_FORMATS[fmap1.dtype],
-                                                  B, D, H, W, q_count, ws.data_ptr(), st), what)
+            pack = lib().ecorr_build_split_pack_hi_as if hi else lib().ecorr_build_split_pack_as
+            check(pack(fmap1.data_ptr(), fmap2.data_ptr(), ELEM_FORMATS[fmap1.dtype], B, D, H, W, q_count,
+                       ws.data_ptr(), st), what)
         if tm is not None:
             ev[1].record()
-        check(lib().ecorr_build_split_gemm(B, D, H, W, q_count, levels, pyr.data_ptr(), ws.data_ptr(), st),
-              what)
+        gemm = lib().ecorr_build_split_gemm_hi if hi else lib().ecorr_build_split_gemm
+        check(gemm(B, D, H, W, q_count, levels, pyr.data_ptr(), ws.data_ptr(), st), what)
         if tm is not None:
             ev[2].record()
             tm.append(ev)

@@ -107,9 +107,11 @@ ECORR_EXPORT int ecorr_pyramid_formats(int H, int W, int levels, int* ntx) {
 
 namespace {
 
-// fmap_format (split build): ECORR_ELEM_* of the elements fmap1 / fmap2 point at
+// fmap_format (split build): ECORR_ELEM_* of the elements fmap1 / fmap2 point at; hi: workspace is a
+// hi workspace (the flag block, then the split workspace)
 int build_common(const float* fmap1, const float* fmap2, int B, int D, int H, int W, int q_count, int levels,
-                 float* pyramid, void* workspace, void* stream, int stages = 3, int fmap_format = ECORR_ELEM_F32) {
+                 float* pyramid, void* workspace, void* stream, int stages = 3, int fmap_format = ECORR_ELEM_F32,
+                 bool hi = false) {
     if ((stages & 1) && (!fmap1 || !fmap2)) return ECORR_EINVAL;
     if ((stages & 2) && !pyramid) return ECORR_EINVAL;
     if (B <= 0 || D <= 0) return ECORR_EINVAL;
@@ -135,9 +137,9 @@ int build_common(const float* fmap1, const float* fmap2, int B, int D, int H, in
     P.scale_shift = P.scale_is_mul ? e - 1 : 0;   // s = 0.5 * 2^e
     if (workspace) {
         if (B > 65535 || ((uintptr_t)workspace & 255)) return ECORR_EINVAL;
-        P.ws = static_cast<char*>(workspace);
+        P.ws = static_cast<char*>(workspace) + (hi ? kHiFlagBytes : 0);
     }
-    return launch_build(P, B, g, pyramid, (hipStream_t)stream, stages, fmap_format);
+    return launch_build(P, B, g, pyramid, (hipStream_t)stream, stages, fmap_format, hi);
 }
 
 }  // namespace
@@ -183,6 +185,34 @@ ECORR_EXPORT int ecorr_build_split_gemm(int B, int D, int H, int W, int q_count,
                                         void* workspace, void* stream) {
     if (!workspace) return ECORR_EINVAL;
     return build_common(nullptr, nullptr, B, D, H, W, q_count, levels, pyramid, workspace, stream, 2);
+}
+
+ECORR_EXPORT int ecorr_build_split_hi_workspace_size(int B, int D, int H, int W, int q_count, int64_t* bytes) {
+    const int st = ecorr_build_split_workspace_size(B, D, H, W, q_count, bytes);
+    if (st == ECORR_OK) *bytes += kHiFlagBytes;
+    return st;
+}
+
+ECORR_EXPORT int ecorr_build_split_pack_hi_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D,
+                                              int H, int W, int q_count, void* workspace, void* stream) {
+    if (!workspace) return ECORR_EINVAL;
+    return build_common((const float*)fmap1, (const float*)fmap2, B, D, H, W, q_count, 1, nullptr, workspace, stream, 1,
+                        fmap_format, true);
+}
+
+ECORR_EXPORT int ecorr_build_split_gemm_hi(int B, int D, int H, int W, int q_count, int levels, float* pyramid,
+                                           void* workspace, void* stream) {
+    if (!workspace) return ECORR_EINVAL;
+    return build_common(nullptr, nullptr, B, D, H, W, q_count, levels, pyramid, workspace, stream, 2, ECORR_ELEM_F32,
+                        true);
+}
+
+ECORR_EXPORT int ecorr_build_split_hi_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H,
+                                         int W, int q_count, int levels, float* pyramid, void* workspace,
+                                         void* stream) {
+    if (!workspace) return ECORR_EINVAL;
+    return build_common((const float*)fmap1, (const float*)fmap2, B, D, H, W, q_count, levels, pyramid, workspace,
+                        stream, 3, fmap_format, true);
 }
 
 namespace {

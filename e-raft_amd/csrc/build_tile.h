@@ -1,5 +1,5 @@
-// build_tile.h -- what the CorrBlock build's GEMM kernels (build.hip, the one translation unit that
-// includes this header) share because it is a property of the tile, not of one kernel: the n-tile
+// build_tile.h -- what the CorrBlock build's GEMM kernels (build.hip and, for the hi-only split16
+// kernels, build_hi.hip: the translation units that include this header) share because it is a property of the tile, not of one kernel: the n-tile
 // geometry and tile order, the operand-panel order of the targets, the pooled-level addressing and
 // descriptors, and the frame of the three 256 x 128 kernels (build_split_kernel,
 // build_split16_kernel, build_f32_kernel): their one LDS array, the per-pixel exponents, the

@@ -78,9 +78,17 @@ struct BuildParams : LevelTable<float> {   // the table: the levels written (tho
 
 // stages (split build only; the fp32 build is one launch): 1 = operand pass, 2 = GEMM + fused
 // pyramid (+ levels > 4), 3 = both.  fmap_format (split build, stage 1): ECORR_ELEM_* of P.f1 / P.f2
+// hi (split build; the ecorr_build_split_*_hi entries): P.ws is a hi workspace's byte kHiFlagBytes, stage
+// 1 zeroes the flag word at P.ws - kHiFlagBytes and, after the operand pass, sets it where a lo half of
+// the panels is non-zero (launch_lo_flag); the D = 241 .. 256 GEMM sums hi*hi alone while it is 0
 int launch_build(const BuildParams& P, int B, const PyrGeom& g, float* pyramid, hipStream_t stream, int stages = 3,
-                 int fmap_format = ECORR_ELEM_F32);
+                 int fmap_format = ECORR_ELEM_F32, bool hi = false);
 int64_t build_split_workspace_bytes(int B, int D, int H, int W, int q_count);
+// build_hi.hip: *flag = 1 if any lo half of the panels [panels, panels + bytes) has a magnitude bit; and
+// the hi-only GEMM of launch_build (hi, D = 241 .. 256) over P's ntiles block tiles
+void launch_lo_flag(const char* panels, int64_t bytes, int* flag, hipStream_t stream);
+void launch_split16_hi(const BuildParams& P, int64_t ntiles, hipStream_t stream);
+constexpr int kHiFlagBytes = 256;   // the flag block in front of a hi workspace: int32 word 0, rest reserved
 
 struct LookupParams : LevelTable<const float> {   // the table: the pyramid (read only)
     const float* coords;  // [B][2][q_count]

@@ -149,6 +149,36 @@ int ecorr_build_split_pack_as(const void* fmap1, const void* fmap2, int fmap_for
 int ecorr_build_split_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
                          int q_count, int levels, float* pyramid, void* workspace, void* stream);
 
+/* The hi-only split build (added within ABI 17: purely additive, the version stays 17): the split
+ * build for fmaps whose elements fit the split's hi half -- every finite binary16 or bfloat16 value,
+ * and every fp32 value with at most 11 significant bits in binary16's range once scaled.  For such
+ * fmaps every lo half of the operand panels is +-0, two of the three MFMAs per product add zeros, and
+ * the GEMM sums hi*hi alone: one MFMA per product and half the panel bytes read.
+ *   _pack_hi_as  ecorr_build_split_pack_as's pass, then a scan of the panels' lo halves that records on
+ *                the device whether any has a magnitude bit (any non-finite element's does: a NaN);
+ *   _gemm_hi     ecorr_build_split_gemm; at D = 241 .. 256 it runs the one-term loop when that record
+ *                is clear and the three-term loop otherwise.  At any other D it is
+ *                ecorr_build_split_gemm's kernel and the record is unused;
+ *   _hi_as       pack_hi_as then gemm_hi.
+ * Bitwise contract: the pyramid is bitwise that of ecorr_build_split_as on the same inputs, whichever
+ * loop ran -- with every lo = +-0 and every hi finite the dropped MFMAs add sums of +-0 to an
+ * accumulator that starts at +0, is never -0 and never subnormal, which leaves its bits alone.  The
+ * caller never learns which loop ran and need not.
+ * workspace: ecorr_build_split_hi_workspace_size() bytes = ecorr_build_split_workspace_size() + 256,
+ * 256-byte aligned.  Its first 256 bytes are the record (int32 word 0: 0 = every lo half is +-0, 1 =
+ * not; the rest reserved); from byte 256 on it is, byte for byte, the workspace ecorr_build_split_pack_as
+ * writes.  _pack_hi_as zeroes word 0 on `stream` (a memset node under graph capture) before its pass.
+ * The two stages take the same workspace and geometry, gemm stream-ordered after pack, as the plain
+ * stages do.  All three ECORR_ELEM_* formats are accepted.  Same argument validation, order and
+ * error codes as the *_as entries; an unknown fmap_format gives ECORR_EINVAL before any launch. */
+int ecorr_build_split_hi_workspace_size(int B, int D, int H, int W, int q_count, int64_t* bytes);
+int ecorr_build_split_pack_hi_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
+                                 int q_count, void* workspace, void* stream);
+int ecorr_build_split_gemm_hi(int B, int D, int H, int W, int q_count, int levels, float* pyramid,
+                              void* workspace, void* stream);
+int ecorr_build_split_hi_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
+                            int q_count, int levels, float* pyramid, void* workspace, void* stream);
+
 /* ---- The backward (ABI 17): gradients of a loss through ecorr_lookup and ecorr_build, coordinates detached ----
  * Deterministic: a query row's gradient images are owned by one workgroup per launch and summed in
  * a fixed order; there are no float atomics, so equal inputs give bitwise equal gradients. */
