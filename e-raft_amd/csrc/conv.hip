@@ -92,28 +92,19 @@ __global__ __launch_bounds__(SNT) void split_pack_kernel(const float* __restrict
 // PRE: `in` is the presplit corr (ecorr_lookup_presplit): the B fragment of chunk c is two 16-byte
 // loads (hi, lo of group 2 c + kh) instead of 8 dword loads and the split, and the query exponent
 // comes from `scale` (qmax unused); the weight columns are packed in the presplit order.
-// The RELU flag rides in PDF = PD | kNoRelu: without it the epilogue skips the ReLU and nothing
-// else changes (grad_in of the backward, conv_grad.hip: the same product with the transposed
-// weight).  It is no third template parameter because that would rename the two forward kernels,
-// whose mangled names tests/test_isa_waits.py looks up; with the flag clear they compile to the
-// instructions they had before (profiles/motion_backward/isa_identity.txt).
-// The output element rides there too, for the same reason: PDF | kOutF16 / kOutBF16 makes `out` a
-// [B][O][Q] array of 2-byte elements (ecorr_conv1x1_relu_split_as; non-presplit only) and the
-// epilogue store one range-checked 2-byte buffer store per (channel, query) of out_elem's convert
-// of the fp32 value (out_elem.h) -- lane = query as before, row o starting at byte 2 o Q, so
-// neighbouring queries are not packed into dwords.
-constexpr int kNoRelu = 0x100;
-constexpr int kOutF16 = 0x200, kOutBF16 = 0x400;
-template <int PDF, bool PRE = false>
+// RELU: false skips the epilogue's ReLU and changes nothing else (grad_in of the backward,
+// conv_grad.hip: the same product with the transposed weight).
+// FMT: ECORR_OUT_F16 / ECORR_OUT_BF16 make `out` a [B][O][Q] array of 2-byte elements
+// (ecorr_conv1x1_relu_split_as; non-presplit only) and the epilogue store one range-checked 2-byte
+// buffer store per (channel, query) of out_elem's convert of the fp32 value (out_elem.h) -- lane =
+// query as before, row o starting at byte 2 o Q, so neighbouring queries are not packed into dwords.
+template <int PD, bool PRE = false, bool RELU = true, int FMT = ECORR_OUT_F32>
 __global__ __launch_bounds__(SNT) void conv1x1_split_kernel(const float* __restrict__ in, int C, int Q,
                                                             const float* __restrict__ qmax, int G,
                                                             const char* __restrict__ packed,
                                                             const float* __restrict__ bias, int O,
                                                             float* __restrict__ out,
                                                             const int* __restrict__ scale) {
-    constexpr int PD = PDF & 0xff;
-    constexpr bool RELU = !(PDF & kNoRelu);
-    constexpr int FMT = (PDF & kOutF16) ? ECORR_OUT_F16 : (PDF & kOutBF16) ? ECORR_OUT_BF16 : ECORR_OUT_F32;
     static_assert(FMT == ECORR_OUT_F32 || !PRE, "16-bit output: the non-presplit kernel only");
     constexpr int ES = sizeof(typename OutElem<FMT>::type);   // output element bytes
     constexpr int NB = 3;
@@ -377,14 +368,14 @@ int launch_conv1x1_relu_split(const float* in, int B, int C, int Q, const float*
     if (!half && out_format != ECORR_OUT_F32) return ECORR_EINVAL;
     const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
     if (out_format == ECORR_OUT_F16)
-        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD | kOutF16, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax,
-                           G, (const char*)packed, bias, O, out, nullptr);
+        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, /*PRE*/ false, /*RELU*/ true, ECORR_OUT_F16>), grid, dim3(SNT),
+                           0, stream, in, C, Q, qmax, G, (const char*)packed, bias, O, out, nullptr);
     else if (out_format == ECORR_OUT_BF16)
-        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD | kOutBF16, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax,
-                           G, (const char*)packed, bias, O, out, nullptr);
+        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, /*PRE*/ false, /*RELU*/ true, ECORR_OUT_BF16>), grid, dim3(SNT),
+                           0, stream, in, C, Q, qmax, G, (const char*)packed, bias, O, out, nullptr);
     else
-        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax, G,
-                           (const char*)packed, bias, O, out, nullptr);
+        hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, /*PRE*/ false, /*RELU*/ true, ECORR_OUT_F32>), grid, dim3(SNT),
+                           0, stream, in, C, Q, qmax, G, (const char*)packed, bias, O, out, nullptr);
     return hip_status();
 }
 
@@ -395,8 +386,8 @@ int launch_conv1x1_split_linear(const float* in, int B, int C, int Q, const floa
     if (!qmax || G <= 0 || !split_geometry_ok(B, C, Q, O, G)) return ECORR_EINVAL;
     if ((const void*)in == (const void*)out) return ECORR_EINVAL;
     const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
-    hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD | kNoRelu, false>), grid, dim3(SNT), 0, stream, in, C, Q, qmax,
-                       G, (const char*)packed, nullptr, O, out, nullptr);
+    hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, /*PRE*/ false, /*RELU*/ false, ECORR_OUT_F32>), grid, dim3(SNT), 0,
+                       stream, in, C, Q, qmax, G, (const char*)packed, nullptr, O, out, nullptr);
     return hip_status();
 }
 
@@ -410,8 +401,8 @@ int launch_conv1x1_relu_presplit(const void* in, int B, int levels, int Q, const
         return ECORR_EINVAL;
     if ((const void*)in == (const void*)out) return ECORR_EINVAL;
     const dim3 grid((unsigned)((Q + SQ - 1) / SQ), (unsigned)split_oblocks(O), (unsigned)B);
-    hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, true>), grid, dim3(SNT), 0, stream, (const float*)in, C, Q,
-                       nullptr, 0, (const char*)packed, bias, O, out, scale);
+    hipLaunchKernelGGL((conv1x1_split_kernel<kConvPD, /*PRE*/ true, /*RELU*/ true, ECORR_OUT_F32>), grid, dim3(SNT), 0,
+                       stream, (const float*)in, C, Q, nullptr, 0, (const char*)packed, bias, O, out, scale);
     return hip_status();
 }
 

@@ -21,11 +21,9 @@ inline unsigned grid_for(int64_t n) {
 }
 
 // Whether the register-column kernel serves P (radius 4 or 1, and a batch item's output within its
-// 32-bit store offsets at `elem` bytes per element), and its staging form: column pairs when every
-// level width is even and every level 8-byte aligned.
+// 32-bit store offsets at `elem` bytes per element), and its staging form (lookup_stage.h).
 inline bool lookup_takes_cols(const LookupParams& P, int elem, bool* pair) {
-    *pair = true;
-    for (int lv = 0; lv < P.levels; ++lv) *pair &= P.lw[lv] % 2 == 0 && (uintptr_t)P.lvl[lv] % 8 == 0;
+    *pair = stage_takes_pairs(P);
     return (P.radius == 4 || P.radius == 1) && (int64_t)P.C * P.q_count * elem < 0x7fffffff;
 }
 

@@ -1,5 +1,6 @@
 // lookup_stage.h -- the per-level window staging shared by the lookup kernel (lookup.hip) and the
-// fused lookup + convc1 kernel (motion.hip).  Device code only, gfx950.
+// fused lookup + convc1 kernel (motion.hip).  Device code (and the one host predicate that picks
+// PAIR staging), gfx950.
 //
 // For a group of QB consecutive queries of one batch item and one pyramid level (NTQ threads,
 // NTQ / QB threads per query):
@@ -30,6 +31,14 @@ namespace ecorr {
 // of an odd origin, or column S of an even one; never read) goes to the dummy slot at the end of win[],
 // so rows hold S slots: 31.7 KB at r = 4, five workgroups per CU (S + 1 slots: 34.8 KB, four;
 // round 3 A/B 41.7 / 45.4 / 41.3 vs 41.9 / 45.8 / 42.8 us on the smooth / sigma-3 / sigma-40 fields).
+// Host side: whether P's windows can be staged as column pairs -- every level width even and every
+// level 8-byte aligned.
+inline bool stage_takes_pairs(const LookupParams& P) {
+    bool pair = true;
+    for (int lv = 0; lv < P.levels; ++lv) pair &= P.lw[lv] % 2 == 0 && (uintptr_t)P.lvl[lv] % 8 == 0;
+    return pair;
+}
+
 template <int R, int QB, bool PAIR = false>
 struct WindowBuf {
     static constexpr int K = 2 * R + 1;   // samples per axis

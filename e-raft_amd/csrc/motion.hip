@@ -224,8 +224,7 @@ int launch_lookup_conv(const LookupParams& P, int B, const float* wt, const floa
     const dim3 grid((unsigned)((P.q_count + QBM - 1) / QBM), (unsigned)B), block(NTM);
     if (out_format != ECORR_OUT_F32 && (!packed || (out_format != ECORR_OUT_F16 && out_format != ECORR_OUT_BF16)))
         return ECORR_EINVAL;
-    bool pair = true;   // column-pair staging: every level width even, 8-byte aligned levels
-    for (int lv = 0; lv < P.levels; ++lv) pair &= P.lw[lv] % 2 == 0 && (uintptr_t)P.lvl[lv] % 8 == 0;
+    const bool pair = stage_takes_pairs(P);
     if (out_format == ECORR_OUT_F16) {
         if (pair) hipLaunchKernelGGL((lookup_conv_kernel<4, true, true, ECORR_OUT_F16>), grid, block, 0, stream, P, wt, bias, O, out);
         else hipLaunchKernelGGL((lookup_conv_kernel<4, false, true, ECORR_OUT_F16>), grid, block, 0, stream, P, wt, bias, O, out);

@@ -2,7 +2,6 @@
 argument validation before any launch, and the store rule of DESIGN §3.1 for csrc/grad.hip."""
 import os
 import subprocess
-import tempfile
 
 import pytest
 
@@ -59,11 +58,9 @@ def test_build_backward_validation(ea):
 def test_grad_hip_store_rule():
     """grad.hip compiled for gfx950 has no wide buffer store whose soffset is an SGPR (the detector of
     tests/test_isa_store_hazard.py)."""
-    from test_isa_store_hazard import CSRC, HIPCC, _asm, scan
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    with tempfile.TemporaryDirectory() as d:
-        ins = _asm(CSRC, "grad", d)
+    from test_isa_store_hazard import _ins, scan
+    from test_isa_waits import listing
+    ins = _ins(listing("grad.hip"))
     assert any(l.startswith("v_mfma_f32_32x32x2") for l in ins), "the backward GEMM should run on the fp32 matrix cores"
     sgpr, hazards = scan(ins)
     assert not sgpr, f"grad.hip: wide buffer stores with an SGPR soffset: {sgpr[:3]}"

@@ -20,36 +20,22 @@ import concurrent.futures
 import os
 import re
 import shutil
-import subprocess
 import sys
 import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "e-raft_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+import isa_listing
+from test_isa_waits import CSRC, HIPCC, ROOT
 
-
-def _makefile_sources():
-    """Every source of libecorr.so: the Makefile's SRCS, without the .hip suffix."""
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        m = re.search(r"^SRCS\s*:=\s*(.*)$", f.read(), re.M)
-    return [s[:-len(".hip")] for s in m.group(1).split() if s.endswith(".hip")] if m else []
-
-
-SOURCES = _makefile_sources()
+SOURCES = isa_listing.sources(CSRC)   # every source of libecorr.so
 WIDE = re.compile(r"buffer_store_(?:dwordx3|dwordx4|b96|b128)\s+v\[(\d+):(\d+)\],\s*\S+,\s*s\[\d+:\d+\],\s*(\S+)")
 VDST = re.compile(r"v_\S+\s+v(?:\[(\d+):(\d+)\]|(\d+))\b")
 
 
-def _asm(src_dir, name, out_dir):
-    out = os.path.join(out_dir, name + ".s")
-    flags = ["-fno-slp-vectorize"] if name == "build" else []
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", *flags,
-                    "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S",
-                    os.path.join(src_dir, name + ".hip"), "-o", out], check=True, capture_output=True)
-    return [l.strip() for l in open(out) if l.startswith("\t") and not l.strip().startswith((".", ";"))]
+def _ins(text):
+    """Every instruction line of a listing, in file order."""
+    return isa_listing.instructions(text.splitlines())
 
 
 def scan(ins):
@@ -86,19 +72,20 @@ def compiled():
             s = open(p).read()
             assert old in s
             open(p, "w").write(s.replace(old, new))
-        with concurrent.futures.ThreadPoolExecutor(8) as ex:
-            jobs = {n: ex.submit(_asm, CSRC, n, d) for n in SOURCES}
-            jobs["soff_full"] = ex.submit(_asm, bad, "build", bad)
-            yield {n: j.result() for n, j in jobs.items()}
+        with concurrent.futures.ThreadPoolExecutor(1) as ex:   # the variant beside the tree's sources
+            soff = ex.submit(isa_listing.listing, bad, "build.hip")
+            res = {n: _ins(t) for n, t in isa_listing.compile_all(CSRC, SOURCES).items()}
+            res["soff_full"] = _ins(soff.result())
+        yield res
     finally:
         shutil.rmtree(d, ignore_errors=True)
 
 
 def test_no_wide_store_with_sgpr_soffset(compiled):
-    assert "build" in SOURCES and "grad" in SOURCES, f"SRCS of the Makefile not read: {SOURCES}"   # build: _asm's flag
+    assert "build.hip" in SOURCES and "grad.hip" in SOURCES, f"SRCS of the Makefile not read: {SOURCES}"
     for n in SOURCES:
         sgpr, hazards = scan(compiled[n])
-        assert not sgpr, f"{n}.hip: wide buffer stores with an SGPR soffset: {sgpr[:3]}"
+        assert not sgpr, f"{n}: wide buffer stores with an SGPR soffset: {sgpr[:3]}"
 
 
 def test_detector_finds_round3_variant(compiled):

@@ -8,7 +8,7 @@ chunk k's DMA pieces.  That count is right only while hipcc
 keeps the source's issue order (sched_barrier fences hold it today; DESIGN.md §3.1 records the
 hoisted q(0) load that once made barrier 0 release a wave before t(0) landed).
 
-This test compiles build.hip for gfx950 (`hipcc --cuda-device-only -S`), replays each kernel's
+This test takes build.hip's gfx950 listing (isa_listing.py: the Makefile's flags), replays each kernel's
 instruction stream up to its K loop's closing barrier and checks, in the order the assembler
 actually emits:
   * RAW: at barrier k (k < NK) every DMA piece of chunk k has retired under the waits issued so far
@@ -24,10 +24,10 @@ A deliberately swapped issue order (q(0) hoisted over t(0)) must be flagged.
 """
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
+
+import isa_listing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "e-raft_amd", "csrc")
@@ -42,26 +42,21 @@ KERNELS = {
 SPLIT = "build_split16_kernelILb1EE"
 
 
-@pytest.fixture(scope="module")
-def asm():
+def listing(src):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "build.s")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-                        "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S",
-                        os.path.join(CSRC, "build.hip"), "-o", out],
-                       check=True, capture_output=True)
-        return open(out).read()
+    isa_listing.compile_all(CSRC)   # the first call compiles all of SRCS side by side, for the three ISA test files
+    return isa_listing.listing(CSRC, src)
+
+
+@pytest.fixture(scope="module")
+def asm():
+    return listing("build.hip")
 
 
 def kernel_loop(s, name):
     """The kernel's instructions up to and including the first s_barrier after its last MFMA."""
-    m = re.search(r"^(_Z\S*" + re.escape(name) + r"\S*):", s, re.M)
-    assert m, f"{name} not in the listing"
-    end = s.find(".Lfunc_end", m.start())
-    ins = [ln.strip() for ln in s[m.start():end].splitlines()
-           if ln.startswith("\t") and not ln.strip().startswith((".", ";"))]
+    ins = isa_listing.find(s, name).ins
     last = max(i for i, ln in enumerate(ins) if ln.startswith("v_mfma"))
     close = next(i for i in range(last, len(ins)) if ins[i] == "s_barrier")
     return ins[:close + 1]
@@ -131,6 +126,14 @@ def check_loop(ins, nbuf, copies, nk, chunk, check_offsets, span=1):
     return errs
 
 
+def hoist_query_loads(ins, n):
+    """The stream with q(0) -- the first n query loads after the first DMA piece -- moved in front of
+    t(0), that piece: the race DESIGN.md §3.1 records."""
+    first = next(i for i, ln in enumerate(ins) if is_dma(ln))
+    q = [i for i, ln in enumerate(ins) if i > first and is_vmem(ln) and not is_dma(ln)][:n]
+    return ins[:first] + [ins[i] for i in q] + [ln for i, ln in enumerate(ins[first:], first) if i not in q]
+
+
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_static_waits_match_issue_order(asm, name):
     k = KERNELS[name]
@@ -147,10 +150,7 @@ def test_checker_flags_a_hoisted_query_load(asm):
     """q(0) moved in front of t(0) -- the race DESIGN.md §3.1 records -- is caught at barrier 0."""
     k = KERNELS[SPLIT]
     ins = kernel_loop(asm, SPLIT)
-    first = next(i for i, ln in enumerate(ins) if is_dma(ln))
-    q = [i for i, ln in enumerate(ins) if i > first and is_vmem(ln) and not is_dma(ln)][:k["qloads"]]
-    swapped = ins[:first] + [ins[i] for i in q] + [ln for i, ln in enumerate(ins[first:], first) if i not in q]
-    errs = check_loop(swapped, k["nbuf"], k["copies"], k["nk"], k["chunk"], True, k["span"])
+    errs = check_loop(hoist_query_loads(ins, k["qloads"]), k["nbuf"], k["copies"], k["nk"], k["chunk"], True, k["span"])
     assert any(e.startswith("barrier 0:") for e in errs), errs
     # and a DMA refill issued one barrier early (WAR on a buffer still being read)
     dmas = [i for i, ln in enumerate(ins) if is_dma(ln)]
@@ -170,28 +170,17 @@ def test_checker_flags_a_hoisted_query_load(asm):
 # prologue + two trips of the loop body + both remainder steps: barriers 0 (prologue) .. 8.
 # The presplit instantiation (PRE = true, ABI 16) loads 2 16-byte pieces per chunk: vmcnt(6) at the
 # step barriers (2 loads + 4 DMA pieces newer than chunk c + 1's).
-CONVS = {"conv1x1_split_kernelILi2ELb0EE": 12, "conv1x1_split_kernelILi2ELb1EE": 6}
+CONVS = {"conv1x1_split_kernelILi2ELb0ELb1ELi0EE": 12, "conv1x1_split_kernelILi2ELb1ELb1ELi0EE": 6}
 
 
 @pytest.fixture(scope="module")
 def conv_asm():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "conv.s")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                        "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S",
-                        os.path.join(CSRC, "conv.hip"), "-o", out],
-                       check=True, capture_output=True)
-        return open(out).read()
+    return listing("conv.hip")
 
 
 def conv_stream(s, name):
     """Straight-line replay of the conv kernel: prologue, loop body twice, the remainder steps."""
-    m = re.search(r"^(_Z\S*" + re.escape(name) + r"\S*):", s, re.M)
-    assert m, f"{name} not in the listing"
-    end = s.find(".Lfunc_end", m.start())
-    lines = s[m.start():end].splitlines()
+    lines = isa_listing.find(s, name).body
     # the K loop: the loop header whose body holds the MFMAs
     heads = [i for i, ln in enumerate(lines) if "Inner Loop Header" in ln]
     head = next(h for h in heads if any("v_mfma" in ln for ln in lines[h:h + 200]))
@@ -201,8 +190,7 @@ def conv_stream(s, name):
     last_bar = max(i for i, ln in enumerate(lines) if ln.strip() == "s_barrier")
 
     def ins(a, b):
-        return [ln.strip() for ln in lines[a:b]
-                if ln.startswith("\t") and not ln.strip().startswith((".", ";"))]
+        return isa_listing.instructions(lines[a:b])
     return ins(0, head) + ins(head, back + 1) * 2 + ins(back + 1, last_bar + 1)
 
 

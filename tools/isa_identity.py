@@ -6,53 +6,26 @@
 
 BEFORE_CSRC / AFTER_CSRC: two copies of e-raft_amd/csrc (each beside its ../../include, e.g. a
 `git worktree` of the parent commit and the working tree).  Every listed source (default: all of
-AFTER's Makefile SRCS; one absent in BEFORE has only-after kernels) is compiled with the Makefile's
-code-generation flags to assembly; per kernel the instruction stream (no directives, comments or label definitions; the function index
-in local labels `.LBB<n>_` dropped, as a kernel added earlier in the file shifts it) and the
-resource block (VGPRs, LDS, scratch) are compared.  One line per kernel: identical / DIFFERS /
-only-before / only-after; exit status 1 when a common kernel differs.  CPU only (hipcc -S).
+AFTER's Makefile SRCS; one absent in BEFORE has only-after kernels) is compiled to assembly with
+the flags its own tree's Makefile gives that object (tests/isa_listing.py); per kernel the
+instruction stream (no directives, comments or label definitions; the function index in local
+labels `.LBB<n>_` dropped, as a kernel added earlier in the file shifts it) and the resource block
+(VGPRs, LDS, scratch) are compared.  One line per kernel: identical / DIFFERS / only-before /
+only-after, the first differing instruction lines under a DIFFERS line; exit status 1 when a
+common kernel differs.  CPU only (hipcc -S).
 
 --renamed REGEX=REPL (repeatable): a kernel of AFTER whose mangled name is absent in BEFORE is
 compared with the BEFORE kernel named re.sub(REGEX, REPL, name), when that exists -- for a kernel
 whose name changed but whose code must not have, e.g. an instantiation that gained a defaulted
-template parameter (`Li0E` appended to its argument list).  Such a line names both kernels.
+template parameter (`Li0E` appended to its argument list).  The first rule that yields a BEFORE
+kernel wins, so specific rules go before general ones.  Such a line names both kernels.
 """
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def sources(csrc):
-    m = re.search(r"^SRCS\s*:=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
-    return m.group(1).split()
-
-
-def kernels(csrc, src, tmp):
-    out = os.path.join(tmp, src + ".s")
-    flags = ["-fno-slp-vectorize"] if src == "build.hip" else []
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", *flags,
-                    "-I" + os.path.join(csrc, "..", "..", "include"), "--cuda-device-only", "-S",
-                    os.path.join(csrc, src), "-o", out], check=True, capture_output=True)
-    s = open(out).read()
-    res = {}
-    for m in re.finditer(r"^(_Z\S+):\s*; @\S+\n(.*?)^\.Lfunc_end\d+:", s, re.M | re.S):
-        name, body = m.group(1), m.group(2)
-        if f".amdhsa_kernel {name}\n" not in s:
-            continue   # a device function, not a kernel
-        ins = [re.sub(r"\.LBB\d+_", ".LBB_", ln.split(";")[0].strip()) for ln in body.splitlines()
-               if ln.startswith("\t") and not ln.strip().startswith((".", ";"))]
-        k = s[s.index(f".amdhsa_kernel {name}\n"):]
-        k = k[:k.index(".end_amdhsa_kernel")]
-
-        def field(f):
-            return int(re.search(r"\." + f + r"\s+(\d+)", k).group(1))
-        res[name] = (ins, field("amdhsa_next_free_vgpr"), field("amdhsa_group_segment_fixed_size"),
-                     field("amdhsa_private_segment_fixed_size"))
-    return res
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import isa_listing  # noqa: E402
 
 
 def main():
@@ -62,38 +35,41 @@ def main():
         renames.append((re.compile(pat), repl))
         args = args[2:]
     before, after, only = args[0], args[1], args[2:]
-    srcs = only or sources(after)
+    srcs = only or isa_listing.sources(after)
+    B = isa_listing.compile_all(after, srcs)
+    A = isa_listing.compile_all(before, [s for s in srcs if os.path.exists(os.path.join(before, s))])   # else: a new file
     bad = 0
-    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        for src in srcs:
-            a = kernels(before, src, ta) if os.path.exists(os.path.join(before, src)) else {}   # a new file
-            b = kernels(after, src, tb)
-            was = {}   # AFTER name -> its BEFORE name, for the renamed kernels
-            for name in b:
-                if name not in a:
-                    for pat, repl in renames:
-                        old = pat.sub(repl, name)
-                        if old != name and old in a and old not in b:
-                            was[name] = old
-                            break
-            for name in sorted((set(a) - set(was.values())) | set(b)):
-                if name in was:
-                    ins, v, l, sc = b[name]
-                    same = a[was[name]] == b[name]
-                    bad += not same
-                    print(f"{src} {name} (before: {was[name]}): {len(ins)} instr, {v} vgpr, {l} lds, {sc} scratch, "
-                          + ("identical" if same else "DIFFERS"))
-                elif name not in b:
-                    print(f"{src} {name}: only-before")
-                elif name not in a:
-                    ins, v, l, sc = b[name]
-                    print(f"{src} {name}: {len(ins)} instr, {v} vgpr, {l} lds, {sc} scratch, only-after")
-                else:
-                    ins, v, l, sc = b[name]
-                    same = a[name] == b[name]
-                    bad += not same
-                    print(f"{src} {name}: {len(ins)} instr, {v} vgpr, {l} lds, {sc} scratch, "
-                          + ("identical" if same else "DIFFERS"))
+    for src in srcs:
+        a = isa_listing.kernels(A[src]) if src in A else {}
+        b = isa_listing.kernels(B[src])
+        was = {}   # AFTER name -> its BEFORE name, for the renamed kernels
+        for name in b:
+            if name not in a:
+                for pat, repl in renames:
+                    old = pat.sub(repl, name)
+                    if old != name and old in a and old not in b:
+                        was[name] = old
+                        break
+        for name in sorted((set(a) - set(was.values())) | set(b)):
+            if name not in b:
+                print(f"{src} {name}: only-before")
+                continue
+            kb, ka = b[name], a.get(was.get(name, name))
+            line = f"{src} {name}" + (f" (before: {was[name]})" if name in was else "")
+            line += f": {len(kb.ins)} instr, {kb.vgpr} vgpr, {kb.lds} lds, {kb.scratch} scratch, "
+            if ka is None:
+                print(line + "only-after")
+                continue
+            same = (ka.ins, ka.vgpr, ka.lds, ka.scratch) == (kb.ins, kb.vgpr, kb.lds, kb.scratch)
+            print(line + ("identical" if same else
+                          f"DIFFERS (before: {len(ka.ins)} instr, {ka.vgpr} vgpr, {ka.lds} lds, {ka.scratch} scratch)"))
+            if not same:
+                bad += 1
+                n = max(len(ka.ins), len(kb.ins))
+                first = next((i for i, (x, y) in enumerate(zip(ka.ins, kb.ins)) if x != y), min(len(ka.ins), len(kb.ins)))
+                for i in range(first, min(first + 4, n)):
+                    print(f"    [{i}] before: {ka.ins[i] if i < len(ka.ins) else '-'}")
+                    print(f"    [{i}] after:  {kb.ins[i] if i < len(kb.ins) else '-'}")
     return 1 if bad else 0
 
 

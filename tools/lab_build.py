@@ -179,13 +179,13 @@ PATCHES["qsnost"] = PATCHES["qs"] + [
 # the tree as it is (the baseline of an A/B against an edited tree)
 PATCHES["base"] = []
 # lookup windows staged one column per work item (b32 loads) instead of 8-byte column pairs
-PATCHES["nopair"] = [("lookup_kernels.h", "    *pair = true;", "    *pair = false;")]
+PATCHES["nopair"] = [("lookup_kernels.h", "    *pair = stage_takes_pairs(P);", "    *pair = false;")]
 # timing only: no window loads for one level (what does each level's staging cost?)
 for _lv in range(4):
     PATCHES[f"lk_skip{_lv}"] = [("lookup_stage.h", "            const bool need = (unsigned)(ry - rlo) < (unsigned)(rhi - rlo);",
                                  f"            const bool need = lv != {_lv} && (unsigned)(ry - rlo) < (unsigned)(rhi - rlo);")]
 PATCHES["lk_prio2"] = [("lookup_kernels.h", "    if (md == 0) {\n        int yo[K];", "    __builtin_amdgcn_s_setprio(2);\n    if (md == 0) {\n        int yo[K];")]
-PATCHES["nopairm"] = [("motion.hip", "    bool pair = true;", "    bool pair = false;")]
+PATCHES["nopairm"] = [("motion.hip", "    const bool pair = stage_takes_pairs(P);", "    const bool pair = false;")]
 # fused lookup + convc1 ablations (timing only, AB_NOCHECK=1): no GEMM phase / no lookup phase
 PATCHES["mo_nogemm"] = [("motion.hip", "    for (int oc = 0; oc < O; oc += OB) {", "    for (int oc = 0; oc < 0; oc += OB) {")]
 PATCHES["mo_nolookup"] = [("motion.hip", "    for (int lv = 0; lv < P.levels; ++lv) {\n        stage_level",
@@ -810,6 +810,13 @@ RETIRED.update({n: "7671499" for n in (
 # build_tile.h: the scale-mode launch became launch_mul, whose kernels take BuildParams alone; the
 # persistent variant's extra tile-count argument has no place in it.
 RETIRED["s16_pers"] = "5b0c790"
+# The hi-only split build (fa928fc) moved build_split16_kernel's K loop and epilogue out of
+# build.hip into build_split16_loop.h / build_split16.h, shared with build_hi.hip, and its stamp
+# points with them: these recipes name build.hip and apply up to the commit before.
+RETIRED.update({n: "a50bd9e" for n in (
+    "gm12", "gm16", "gm2", "gm3", "gm4", "gm6", "gm8", "gm9", "l0c1k", "l0contig", "onecu16", "prio_epi", "prio_loop",
+    "s16_agpr", "s16_noepi", "s16_rd8", "st16", "st16_gm12", "st16_gm16", "st16_gm2", "st16_gm4", "st16_gm8", "st16_gm9",
+    "st16_noscale", "st16_prio_loop", "st16_s16stoob", "st16_sscale", "st23_plain", "st23_sc1", "st3_plain")})
 
 
 def build(name):
