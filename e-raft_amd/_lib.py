@@ -74,6 +74,12 @@ SYMBOLS = {
     # a 16-bit (or fp32) output element (added within ABI 17):
     # (pyramid, coords, B, H, W, q_count, levels, radius, out_format, out, stream)
     "ecorr_lookup_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    # volume-free correlation (added within ABI 17): (B, D, H, W, levels, floats*) /
+    # (fmap1, fmap2, fmap_format, B, D, H, W, levels, feat, stream) /
+    # (feat, coords, B, D, H, W, levels, radius, out, out_format, stream)
+    "ecorr_alt_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_alt_pack_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "ecorr_alt_lookup_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p]),
     # the backward (ABI 17): (grad_out, coords, B, H, W, q_count, levels, radius, grad_pyramid, stream)
     "ecorr_lookup_backward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     # (grad_pyramid, fmap1, fmap2, B, D, H, W, q_count, levels, grad_fmap1, grad_fmap2, stream)

@@ -456,6 +456,86 @@ ECORR_EXPORT int ecorr_conv1x1_relu_presplit(const void* in, int B, int levels, 
     return launch_conv1x1_relu_presplit(in, B, levels, Q, scale, packed, bias, O, out, (hipStream_t)stream);
 }
 
+// ---- volume-free correlation (alt.hip) ----
+namespace ecorr {
+
+int alt_geometry(int B, int D, int H, int W, int levels, AltGeom* g) {
+    if (B < 1 || B > 65535 || D < 1 || H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff) return ECORR_EINVAL;
+    if (levels < 1 || levels > ECORR_MAX_LEVELS) return ECORR_EINVAL;
+    if (D > 0x7fffffff - 3) return ECORR_EINVAL;
+    g->levels = levels;
+    g->Dp = (D + 3) & ~3;
+    int64_t o = (int64_t)B * H * W * g->Dp;   // fmap1 first
+    for (int i = 0; i < levels; ++i) {
+        const int hh = H >> i, ww = W >> i;
+        if (hh == 0 || ww == 0) return ECORR_EINVAL;
+        // the kernels' offsets inside one batch item's level are 32-bit byte offsets
+        if ((int64_t)hh * ww * g->Dp * 4 > 0x7fffffff) return ECORR_EINVAL;
+        g->h[i] = hh;
+        g->w[i] = ww;
+        g->off[i] = o;
+        o += (int64_t)B * hh * ww * g->Dp;
+    }
+    g->off[levels] = o;
+    return ECORR_OK;
+}
+
+}  // namespace ecorr
+
+namespace {
+
+bool elem_format_ok(int f) { return f == ECORR_ELEM_F32 || f == ECORR_ELEM_F16 || f == ECORR_ELEM_BF16; }
+
+}  // namespace
+
+ECORR_EXPORT int ecorr_alt_size(int B, int D, int H, int W, int levels, int64_t* floats) {
+    if (!floats) return ECORR_EINVAL;
+    AltGeom g;
+    const int st = alt_geometry(B, D, H, W, levels, &g);
+    if (st != ECORR_OK) return st;
+    *floats = g.off[levels];
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_alt_pack_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
+                                   int levels, float* feat, void* stream) {
+    if (!fmap1 || !fmap2 || !feat || ((uintptr_t)feat & 15) || !elem_format_ok(fmap_format)) return ECORR_EINVAL;
+    AltGeom g;
+    const int st = alt_geometry(B, D, H, W, levels, &g);
+    if (st != ECORR_OK) return st;
+    return launch_alt_pack(fmap1, fmap2, fmap_format, B, D, H, W, g, feat, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_alt_lookup_as(const float* feat, const float* coords, int B, int D, int H, int W, int levels,
+                                     int radius, void* out, int out_format, void* stream) {
+    if (!feat || !coords || !out || ((uintptr_t)feat & 15) || !elem_format_ok(out_format)) return ECORR_EINVAL;
+    if (radius < 0 || radius > 32) return ECORR_EINVAL;
+    AltGeom g;
+    const int st = alt_geometry(B, D, H, W, levels, &g);
+    if (st != ECORR_OK) return st;
+    AltParams P{};
+    P.f1 = feat;
+    for (int i = 0; i < levels; ++i) {
+        P.lvl[i] = feat + g.off[i];
+        P.lh[i] = g.h[i];
+        P.lw[i] = g.w[i];
+    }
+    P.coords = coords;
+    P.out = out;
+    P.B = B;
+    P.Dp = g.Dp;
+    P.Q = H * W;
+    P.levels = levels;
+    P.radius = radius;
+    P.C = levels * (2 * radius + 1) * (2 * radius + 1);
+    // the build's scale step (build_common): / sqrtf(D), a multiply where that is a power of two
+    const float s = sqrtf((float)D);
+    int e = 0;
+    P.scale_is_mul = frexpf(s, &e) == 0.5f ? 1 : 0;
+    P.scale = P.scale_is_mul ? 1.0f / s : s;
+    return launch_alt_lookup(P, out_format, (hipStream_t)stream);
+}
+
 ECORR_EXPORT int ecorr_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                                         int Hg, int Wg, float* out, float* mask, void* stream) {
     if (!img || !coords || !out || N <= 0 || C < 0 || h <= 0 || w <= 0 || Hg <= 0 || Wg <= 0)

@@ -195,6 +195,28 @@ int launch_conv1x1_relu_presplit(const void* in, int B, int levels, int Q, const
 int launch_split_column_scale(const float* f1, const float* f2, int B, int D, int H, int W, int* scale,
                               hipStream_t stream);
 
+// alt.hip: the volume-free lookup (ecorr_alt_*, include/ecorr.h).  The feature buffer's geometry,
+// computed once by alt_geometry() and shared by the pack and the lookup.
+struct AltGeom {
+    int levels, Dp;                                  // Dp: D rounded up to a multiple of 4
+    int h[ECORR_MAX_LEVELS], w[ECORR_MAX_LEVELS];   // pooled fmap2 level sizes
+    int64_t off[ECORR_MAX_LEVELS + 1];               // float offset of each fmap2 level (fmap1 at 0); off[levels] = total
+};
+int alt_geometry(int B, int D, int H, int W, int levels, AltGeom* g);
+struct AltParams {
+    const float* f1;                   // [B][Q][Dp]
+    const float* lvl[ECORR_MAX_LEVELS];   // [B][h w][Dp]
+    int lh[ECORR_MAX_LEVELS], lw[ECORR_MAX_LEVELS];
+    const float* coords;               // [B][2][Q]
+    void* out;                         // [B][C][Q] elements of the launch's out_format
+    int B, Dp, Q, levels, radius, C;
+    float scale;                       // the build's scale step (abi.hip build_common)
+    int scale_is_mul;
+};
+int launch_alt_pack(const void* f1, const void* f2, int fmap_format, int B, int D, int H, int W, const AltGeom& g,
+                    float* feat, hipStream_t stream);
+int launch_alt_lookup(const AltParams& P, int out_format, hipStream_t stream);
+
 int launch_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                             int Hg, int Wg, float* out, float* mask, hipStream_t stream);
 

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .alt_corr import AlternateCorrBlock
 from .corr import CorrBlock
 from .flow import upsample_flow as hip_upsample_flow
 from .utils import coords_grid
@@ -208,6 +209,11 @@ class ERAFT(nn.Module):
     _native_half_lookup=False (private: the A/B arm of the tests, tools/bench_lookup_half.py and
     tools/bench_half_io.py) is the whole path without any of the three: the fmaps go back to fp32
     (.float()), the lookup and lookup_conv1x1_relu return fp32 and autocast casts them.
+    alternate_corr=True (keyword only) serves the lookups from AlternateCorrBlock (alt_corr.py, DESIGN.md
+    §3.10): no all-pairs volume is built, memory grows with H W instead of (H W)^2 and each lookup costs
+    more time.  It composes with mixed_precision (16-bit fmaps in, 16-bit lookup out) and hip_upsample; it
+    is forward-only and has no fused convc1, so fuse_motion_corr, train_motion_corr and
+    differentiable_corr raise ValueError with it.
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
@@ -215,8 +221,12 @@ class ERAFT(nn.Module):
 
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
                  differentiable_corr=False, train_motion_corr=False, mixed_precision=False,
-                 amp_dtype=torch.float16, _native_half_lookup=True):
+                 amp_dtype=torch.float16, _native_half_lookup=True, *, alternate_corr=False):
         super().__init__()
+        if alternate_corr and (fuse_motion_corr or train_motion_corr or differentiable_corr):
+            raise ValueError("alternate_corr=True cannot be combined with fuse_motion_corr, train_motion_corr or "
+                             "differentiable_corr: AlternateCorrBlock is forward-only and has no fused convc1")
+        self.alternate_corr = bool(alternate_corr)
         if amp_dtype not in (torch.float16, torch.bfloat16):
             raise TypeError(f"amp_dtype must be torch.float16 or torch.bfloat16 (got {amp_dtype!r})")
         self.mixed_precision = bool(mixed_precision)
@@ -282,12 +292,13 @@ class ERAFT(nn.Module):
         # differentiable_corr: gradients reach fnet through the HIP backward (corr.py); the keywords
         # are passed only on their paths, so a reference-signature CorrBlock can stand in otherwise
         kw = {"differentiable": True} if self.differentiable_corr else {}
+        block = AlternateCorrBlock if self.alternate_corr else CorrBlock   # the volume-free lookup, or the pyramid
         if half_lookup and fmap1.dtype == self.amp_dtype and fmap2.dtype == self.amp_dtype:
-            corr_fn = CorrBlock(fmap1.contiguous(), fmap2.contiguous(), num_levels=self.corr_levels,
-                                radius=self.corr_radius, fmap_dtype=self.amp_dtype, **kw)
+            corr_fn = block(fmap1.contiguous(), fmap2.contiguous(), num_levels=self.corr_levels,
+                            radius=self.corr_radius, fmap_dtype=self.amp_dtype, **kw)
         else:
-            corr_fn = CorrBlock(fmap1.float().contiguous(), fmap2.float().contiguous(),
-                                num_levels=self.corr_levels, radius=self.corr_radius, **kw)
+            corr_fn = block(fmap1.float().contiguous(), fmap2.float().contiguous(),
+                            num_levels=self.corr_levels, radius=self.corr_radius, **kw)
         with self._autocast():
             net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
             net, inp = torch.tanh(net), torch.relu(inp)

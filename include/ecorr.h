@@ -428,6 +428,34 @@ int ecorr_voxel_grid_dsec(const float* p, const float* t, const float* x, const 
 int ecorr_voxel_grid_mvsec(const double* events, int64_t n, int C, int H, int W, int normalize, float* voxel,
                            int* bad_index, void* workspace, void* stream);
 
+/* ---- Volume-free correlation (three entries added within ABI 17: purely additive, the version stays 17) ----
+ * The lookup of ecorr_build + ecorr_lookup without the all-pairs volume (csrc/alt.hip): the block keeps
+ * the feature maps, channel-last, and every lookup computes the correlation values its samples need.
+ * avg_pool2d over the target axes is linear, so level i of the volume is fmap1^T pool^i(fmap2) / sqrt(D)
+ * with the pyramid's own floor-halving 2 x 2 mean; the arithmetic is reordered, so a result equals the
+ * volume lookup's up to rounding, not bit for bit, while sample positions, NaN samples, exact zeros and
+ * contributing corners are the volume lookup's by construction (the same device functions).  A corner
+ * value is an fp32 dot product of the query's features with one pooled fmap2 pixel, then the build's
+ * scale step (/ sqrtf(D), a multiply where that is a power of two).  No atomics: bitwise reproducible.
+ *
+ * Feature buffer (ecorr_alt_size floats, 16-byte aligned), Dp = D rounded up to a multiple of 4, pad
+ * channels zero:  fmap1 as float[B][H*W][Dp], then for each level i the pooled fmap2 as
+ * float[B][h_i*w_i][Dp], h_i = H >> i, w_i = W >> i, pooled level from level as (((a+b)+c)+d) * 0.25f.
+ * ecorr_alt_pack_as reads fmaps of fmap_format (ECORR_ELEM_*: the conversion is exact) in the build's
+ * [B][D][H][W] order.  ecorr_alt_lookup_as: coords float[B][2][H*W]; out: B * levels*(2r+1)^2 * H*W
+ * elements of out_format (ECORR_OUT_*) in ecorr_lookup's order, each the fp32 sample rounded once.
+ * Radii <= 4 run one wave per (query, level): at most (2r+3)^2 window dot products, then the blends;
+ * larger radii, and queries whose window does not fit (NaN / inf / huge coordinates), compute the
+ * up to four in-image corner dots of each sample.
+ * Errors (before any GPU call), all ECORR_EINVAL: a null pointer, B, D, H or W < 1, levels outside
+ * [1, ECORR_MAX_LEVELS], a level of 0 pixels, radius outside [0, 32], an unknown format, a feature buffer
+ * that is not 16-byte aligned, and a level of one batch item beyond 2^31 bytes (h_i*w_i*Dp*4). */
+int ecorr_alt_size(int B, int D, int H, int W, int levels, int64_t* floats);
+int ecorr_alt_pack_as(const void* fmap1, const void* fmap2, int fmap_format, int B, int D, int H, int W,
+                      int levels, float* feat, void* stream);
+int ecorr_alt_lookup_as(const float* feat, const float* coords, int B, int D, int H, int W, int levels,
+                        int radius, void* out, int out_format, void* stream);
+
 /* Tile shape of the pyramid storage (ECORR_TILE_H, ECORR_TILE_W). */
 int ecorr_pyramid_tile(int* tile_h, int* tile_w);
 
