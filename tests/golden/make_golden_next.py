@@ -21,7 +21,8 @@ on torch-CPU; inputs are drawn from tests/prng.py and stored alongside the refer
                     EventSequenceToVoxelGrid_Pytorch (:36-126) on prng.dsec_events /
                     prng.mvsec_events (seeds stored), normalize off and on, with torch pinned to
                     one thread as main.py:2-5 does; edge cases: constant timestamps, NaN
-                    coordinates, one hot pixel, an out-of-grid MVSEC index (raises).
+                    coordinates, one hot pixel, an out-of-grid MVSEC index (raises), one and two
+                    events (equal and distinct timestamps).
 """
 import os
 import sys

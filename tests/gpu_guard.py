@@ -3,6 +3,10 @@
 guarded / check_guarded: an output handed to a kernel lies in the middle of a buffer filled with one
 bit pattern, GUARD floats of it on each side: a store outside the output changes a guard band, an
 element the kernel never wrote keeps the pattern.
+guarded_u8 / check_guarded_u8: the same for a byte output (the splat's valid mask), BYTE_FILL = 0x7b being
+neither 0 nor 1.
+Workspace: a kernel's byte scratch of exactly the size its size entry reports, WS_GUARD bytes of guard
+on each side, everything prefilled with a byte the caller chooses; a zero-byte one is passed as NULL.
 mismatch: the text of a failed bitwise comparison.
 GRID_STRIDE_THREADS: the threads of one pass of the generic kernels' grid-stride loops.
 """
@@ -10,6 +14,9 @@ import numpy as np
 
 GUARD = 64            # floats on each side of an output (256 bytes: the output keeps its alignment)
 FILL = 0x7b7b7b7b     # 1.3e36 as a float: finite, not NaN, and nothing the kernels under test compute
+BYTE_FILL = 0x7b      # one byte of FILL
+WS_GUARD = 4096       # bytes on each side of a workspace (a multiple of 256: the middle keeps its alignment);
+                      # an overrun of a few hundred bytes still lands in the guard, not beyond it
 GRID_STRIDE_THREADS = 8192 * 256   # grid_for() (csrc/lookup_kernels.h): at most 8192 blocks of NT = 256 threads
 
 
@@ -29,6 +36,43 @@ def check_guarded(buf, what):
     left = int((mid == FILL).sum())
     assert left == 0, f"{what}: {left} of {mid.size} elements were never written"
     return mid.view(np.float32)
+
+
+def guarded_u8(n, device="cuda"):
+    """(the whole uint8 buffer, its middle n bytes), BYTE_FILL everywhere."""
+    import torch
+    buf = torch.full((n + 2 * 4 * GUARD,), BYTE_FILL, dtype=torch.uint8, device=device)
+    return buf, buf[4 * GUARD:4 * GUARD + n]
+
+
+def check_guarded_u8(buf, what):
+    """As check_guarded for a guarded_u8 buffer -> the middle as numpy uint8."""
+    host = buf.cpu().numpy()
+    G = 4 * GUARD
+    assert (host[:G] == BYTE_FILL).all() and (host[-G:] == BYTE_FILL).all(), f"{what}: a guard band was written"
+    mid = host[G:-G]
+    left = int((mid == BYTE_FILL).sum())
+    assert left == 0, f"{what}: {left} of {mid.size} bytes were never written"
+    return mid
+
+
+class Workspace:
+    """nbytes of scratch between two WS_GUARD-byte guards, everything the byte `fill`.  ptr: the
+    middle's address (256-byte aligned), or None (NULL, as _lib.ptr(None)) for a zero-byte workspace."""
+
+    def __init__(self, nbytes, fill, device="cuda"):
+        import torch
+        self.nbytes, self.fill = int(nbytes), fill
+        self.buf = torch.full((self.nbytes + 2 * WS_GUARD,), fill, dtype=torch.uint8, device=device)
+        middle = self.buf.data_ptr() + WS_GUARD
+        assert middle % 256 == 0
+        self.ptr = middle if self.nbytes else None
+
+    def check(self, what):
+        """Asserts both guards untouched."""
+        lo, hi = self.buf[:WS_GUARD], self.buf[WS_GUARD + self.nbytes:]
+        assert bool((lo == self.fill).all()) and bool((hi == self.fill).all()), \
+            f"{what}: a workspace guard was written (workspace of {self.nbytes} bytes)"
 
 
 def mismatch(got, want):

@@ -6,8 +6,8 @@ Raw C ABI calls (ecorr_build_split, ecorr_build_split_pack + ecorr_build_split_g
 Per case and input set:
   - the pyramid lies between two guard bands of gpu_guard.FILL and is pre-filled with it: the guards
     must be intact, every valid element of every level overwritten (padding cells may be either);
-  - split mode: the workspace has exactly ecorr_build_split_workspace_size bytes between 256-byte
-    guards, all pre-filled with 0x7E, so a panel or exponent byte the GEMM reads and the operand
+  - split mode: the workspace has exactly ecorr_build_split_workspace_size bytes between
+    guards (gpu_guard.Workspace), all pre-filled with 0x7E, so a panel or exponent byte the GEMM reads and the operand
     pass never wrote poisons the result (0x7E7E is an f16 NaN, 0x7E7E7E7E a scale of 2^-2e9); the
     guards must be intact; pack + gemm on a second such workspace must give the same pyramid bit
     for bit (the whole buffer, padding included);
@@ -36,7 +36,6 @@ import oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-WS_GUARD = 256        # bytes on each side of the split workspace (keeps its 256-byte alignment)
 WS_FILL = 0x7E
 
 
@@ -68,19 +67,6 @@ def _bits(t):
     return t.contiguous().view(torch.int32)
 
 
-class _Workspace:
-    """nb bytes between two WS_GUARD-byte guards, everything WS_FILL."""
-
-    def __init__(self, nb):
-        self.buf = torch.full((nb + 2 * WS_GUARD,), WS_FILL, dtype=torch.uint8, device=DEV)
-        self.ptr = self.buf.data_ptr() + WS_GUARD
-        assert self.ptr % 256 == 0
-
-    def assert_guards(self, what):
-        lo, hi = self.buf[:WS_GUARD], self.buf[-WS_GUARD:]
-        assert bool((lo == WS_FILL).all()) and bool((hi == WS_FILL).all()), f"{what}: a workspace guard was written"
-
-
 def _build(name, f1, f2, two_stage=False):
     """One build of the case through the C ABI -> (the whole guarded int32 buffer, its pyramid part)."""
     from eraft_amd import _lib
@@ -95,7 +81,7 @@ def _build(name, f1, f2, two_stage=False):
         if mode == "split":
             nb = ctypes.c_int64()
             _lib.check(L_.ecorr_build_split_workspace_size(B, D, H, W, q, ctypes.byref(nb)), what)
-            ws = _Workspace(nb.value)
+            ws = gpu_guard.Workspace(nb.value, WS_FILL, DEV)
             if two_stage:
                 _lib.check(L_.ecorr_build_split_pack(f1.data_ptr(), f2.data_ptr(), B, D, H, W, q, ws.ptr, st), what)
                 _lib.check(L_.ecorr_build_split_gemm(B, D, H, W, q, L, pyr.data_ptr(), ws.ptr, st), what)
@@ -103,7 +89,7 @@ def _build(name, f1, f2, two_stage=False):
                 _lib.check(L_.ecorr_build_split(f1.data_ptr(), f2.data_ptr(), B, D, H, W, q, L, pyr.data_ptr(),
                                                 ws.ptr, st), what)
             torch.cuda.synchronize()
-            ws.assert_guards(what)
+            ws.check(what)
             del ws
         else:
             _lib.check(L_.ecorr_build(f1.data_ptr(), f2.data_ptr(), B, D, H, W, q, L, pyr.data_ptr(), st), what)

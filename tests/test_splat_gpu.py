@@ -54,7 +54,7 @@ def test_grid_sample_values_goldens(ea, splat):
     (16, 60, 80, 1.5),     # DSEC warm start (configs[1])
     (64, 32, 32, 1.5),     # MVSEC (configs[2])
     (4, 92, 160, 3.0),     # 1280x720 (configs[4])
-    (1, 130, 140, 4.0),    # > 16384 targets: counts in the workspace instead of LDS
+    (1, 130, 140, 4.0),    # > 16384 targets, still the banded kernel (n <= 65536): 9 bands of at most 2048 targets
     (1, 264, 300, 3.0),    # > 65536 points: the one-workgroup-per-item kernel and its workspace
     (2, 7, 300, 40.0),     # mostly out of the image
 ])
