@@ -258,6 +258,14 @@ def stream_of(t: torch.Tensor):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def refuse_capture(what: str):
+    """For the entry points that read an error flag on the host: they cannot be part of a HIP graph and
+    say so themselves, before anything is launched."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what} reads an error flag on the host and cannot be captured into a HIP graph "
+                           "(torch.cuda.graph): call it outside the captured region")
+
+
 def tensor_version(t: torch.Tensor) -> int:
     """t's version counter, -1 for an inference tensor: it has none (in-place updates, legal under
     inference_mode, are then not seen)."""

@@ -89,7 +89,9 @@ def flow_to_png16(flow):
 def flow_16bit_to_float(flow_16bit):
     """dsec_utils.py:66-83: uint16 [h, w, 3] -> (flow [h, w, 2] float32, valid [h, w] bool).
     The reference returns float64; every value (v - 2^15) / 128 is exact in float32.  Raises
-    AssertionError where the reference asserts (dtype, shape, channel 2 outside {0, 1})."""
+    AssertionError where the reference asserts (dtype, shape, channel 2 outside {0, 1}).  Not capturable
+    (the channel-2 flag is read on the host): under a graph capture it raises RuntimeError."""
+    _lib.refuse_capture("flow_16bit_to_float")
     if not isinstance(flow_16bit, torch.Tensor):
         raise TypeError("flow_16bit must be a torch.Tensor")
     assert flow_16bit.dtype == torch.uint16

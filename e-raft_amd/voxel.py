@@ -60,6 +60,8 @@ class EventSequenceToVoxelGrid_Pytorch:
         self.device = torch.device("cuda", gpu_nr)   # gpu=False is served on the device too
 
     def __call__(self, event_sequence):
+        # not capturable: the out-of-range flag is read on the host
+        _lib.refuse_capture("EventSequenceToVoxelGrid_Pytorch.__call__")
         events = event_sequence.features
         width, height = event_sequence.image_width, event_sequence.image_height
         assert events.shape[1] == 4

@@ -4,6 +4,8 @@ warm-start splat and the convex upsampling can be captured into one HIP graph
 import pytest
 import torch
 
+from graph_capture import _capture
+
 pytestmark = pytest.mark.gpu
 
 
@@ -14,19 +16,6 @@ def ea():
     import eraft_amd
     eraft_amd.lib()
     return eraft_amd
-
-
-def _capture(fn):
-    dev = torch.device("cuda", 0)
-    s = torch.cuda.Stream(dev)
-    s.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(s):
-        fn()   # warm-up on a side stream, as torch.cuda.graphs recommends
-    torch.cuda.current_stream(dev).wait_stream(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        fn()
-    return g
 
 
 @pytest.mark.parametrize("B,H,W", [(1, 32, 32), (4, 60, 80)])

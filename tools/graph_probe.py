@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Launch-bound regime (BASELINE configs[2]-like, small volumes): CorrBlock build + 12 lookups and
 the full ERAFT.forward, eager vs captured into one HIP graph (torch.cuda.CUDAGraph; the C-ABI
-launches ride the capturing stream).  Prints per-step times and checks replay == eager bitwise."""
+launches ride the capturing stream).  Prints per-step times.  The capture is tests/graph_capture.py's; the
+replay == eager column is a convenience, the check itself is tests/test_graph_paths_gpu.py."""
 import os
 import statistics
 import sys
@@ -15,6 +16,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 import eraft_amd  # noqa: E402
 import eraft_amd.network as nw  # noqa: E402
 from e2e_weights import make_state_dict  # noqa: E402
+from graph_capture import _capture  # noqa: E402
 
 dev = torch.device("cuda", 0)
 
@@ -47,14 +49,7 @@ def corr_case(B, H, W):
     with torch.no_grad():
         step()
         eager = [o.clone() for o in outs]
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            step()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            step()
+        graph = _capture(step)
         graph.replay()
         torch.cuda.synchronize()
         same = all(torch.equal(a, b) for a, b in zip(eager, outs))
@@ -78,14 +73,7 @@ def eraft_case(B, H, W, bins):
     with torch.no_grad():
         step()
         eager = (res["low"].clone(), res["up"].clone())
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            step()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            step()
+        graph = _capture(step)
         graph.replay()
         torch.cuda.synchronize()
         same = torch.equal(eager[0], res["low"]) and torch.equal(eager[1], res["up"])
