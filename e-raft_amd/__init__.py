@@ -3,7 +3,8 @@
 Drop-in for wzygzlm/E-RAFT's model/corr.py and the model/utils.py hot-path helpers:
 
     from eraft_amd import CorrBlock, bilinear_sampler, coords_grid
-    from eraft_amd import AlternateCorrBlock    # CorrBlock's lookup without the all-pairs volume
+    from eraft_amd import AlternateCorrBlock    # CorrBlock's lookup without the all-pairs volume;
+                                                # trainable=True: gradients for the fmaps, still without it
 
 The package lives in the hyphenated directory e-raft_amd/; the root module eraft_amd.py makes it
 importable as `eraft_amd`.  Kernels: e-raft_amd/csrc (HIP, C ABI include/ecorr.h).

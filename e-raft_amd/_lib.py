@@ -80,6 +80,12 @@ SYMBOLS = {
     "ecorr_alt_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "ecorr_alt_pack_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     "ecorr_alt_lookup_as": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p]),
+    # its backward (added within ABI 17): (B, H, W, levels, radius, bytes*) /
+    # (feat, coords, grad_out, B, D, H, W, levels, radius, grad_feat, workspace, stream) /
+    # (grad_feat, B, D, H, W, levels, grad_fmap1, grad_fmap2, stream)
+    "ecorr_alt_backward_workspace_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_alt_lookup_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ecorr_alt_pack_backward": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p]),
     # the backward (ABI 17): (grad_out, coords, B, H, W, q_count, levels, radius, grad_pyramid, stream)
     "ecorr_lookup_backward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     # (grad_pyramid, fmap1, fmap2, B, D, H, W, q_count, levels, grad_fmap1, grad_fmap2, stream)

@@ -3,6 +3,7 @@
     corr_fn = AlternateCorrBlock(fmap1, fmap2, num_levels=4, radius=4)
     corr    = corr_fn(coords1)                               # [B, num_levels * (2r+1)^2, H, W]
     corr    = corr_fn(coords1, out_dtype=torch.float16)      # the same lookup, 16-bit elements
+    corr_fn = AlternateCorrBlock(fmap1, fmap2, trainable=True)   # ... with gradients for the fmaps
 
 The same function as CorrBlock(fmap1, fmap2, num_levels, radius)(coords) -- shape, channel order
 (2r+1)^2 i + (2r+1) a + b, zeros padding and the align_corners=True round trip -- computed without the
@@ -16,11 +17,33 @@ with Q = H W instead of Q^2 (DSEC, B = 16: 183 MB of features against a 1.96 GB 
 far more time than the volume lookup's gather (README.md), so CorrBlock stays the right
 choice wherever its pyramid fits.
 
-The checks and messages are CorrBlock's.  The block is forward-only: fmaps or coords that require grad
-while grad mode is on raise, and so do differentiable=True, corr_pyramid (there is no volume) and
-lookup_conv1x1_relu (no fused convc1).  D = 0 and empty shapes raise: there is no volume to be NaN.
+The checks and messages are CorrBlock's.  By default the block is forward-only: fmaps or coords that
+require grad while grad mode is on raise, and so do differentiable=True (CorrBlock's keyword: the
+opt-in here is trainable=True), corr_pyramid (there is no volume) and lookup_conv1x1_relu (no fused
+convc1).  D = 0 and empty shapes raise: there is no volume to be NaN.
 fmap_dtype / out_dtype: as CorrBlock's (16-bit fmaps are read as they are, exactly; a 16-bit output is
 the fp32 sample rounded once, bitwise corr_fn(coords).to(out_dtype)).  Deterministic (no atomics).
+
+Training (opt-in): AlternateCorrBlock(fmap1, fmap2, num_levels, radius, trainable=True) accepts fmaps
+that require grad and gives them gradients through every `corr_fn(coords)` lookup without a gradient
+pyramid (csrc/alt_grad.hip): where a differentiable CorrBlock holds the pyramid and
+one more pyramid-sized gradient buffer, this block holds the features, one feature-sized gradient
+buffer and, during a lookup's backward, a workspace of the queries' window gradients.  The live rule
+is CorrBlock's: the gradient path is live when trainable is set, grad mode is on and an fmap requires
+grad; otherwise the block is the plain block (and without trainable, fmaps that require grad still
+raise "forward-only").  The forward of a live block runs the same launches, so its values are bitwise
+the plain block's.  Autograd structure as corr.py's: the pack is a Function of the fmaps returning a
+one-element handle, each lookup a Function of (handle, coords) that saves only coords and whose
+backward adds its contribution into the block's gradient feature buffer (allocated and zeroed on the
+first one) and returns a zero for the handle; the pack's backward then runs once, after all of them,
+turns the buffer into the two fmap gradients and frees it.  The backward reads the block's own fp32
+copy of the features, so no fmap is saved and an in-place change of an fmap after construction does
+not affect (or invalidate) the backward: the gradients are those of the values the block was built
+from.  Deterministic (no atomics).  Contract of the live block, as the differentiable CorrBlock's:
+coords are detached (coords.requires_grad raises; there is no coordinate gradient), every level is at
+least 2 x 2, one backward per block (a second one raises), first order only, single GPU.  With a
+16-bit fmap_dtype the gradients are the fp32 result cast once to the fmaps' dtype; with a 16-bit
+out_dtype the backward runs on grad_out.float().
 """
 import torch
 
@@ -28,17 +51,115 @@ from . import _lib
 from ._lib import no_grad_inputs, require_device
 
 
-class AlternateCorrBlock:
-    """Volume-free correlation lookup (module docstring); the interface of CorrBlock's forward."""
+class _AltGradState:
+    """What the backward of one trainable block shares: the geometry, the block's feature buffer, the
+    gradient feature buffer (allocated by the first lookup backward, freed by the pack backward) and
+    the consumed flag.  It references neither the block nor the handle: no cycle in the autograd graph."""
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, fmap_dtype=None, differentiable=False):
+    def __init__(self, shape, levels, radius, feat, device):
+        self.shape, self.levels, self.radius, self.feat, self.device = shape, levels, radius, feat, device
+        self.grad_feat = None
+        self.consumed = False
+
+    def require_unconsumed(self):
+        if self.consumed:
+            raise RuntimeError("eraft_amd AlternateCorrBlock: backward through a block whose gradient was already "
+                               "consumed (one backward per trainable block)")
+
+    def add_lookup_grad(self, grad, coords):
+        """grad_feat += the lookup's contribution: grad (contiguous fp32 [B, C, H, W]) at contiguous
+        coords, on grad's current stream.  The caller holds the device (on_device)."""
+        B, D, H, W = self.shape
+        what = "AlternateCorrBlock lookup backward"
+        if self.grad_feat is None:
+            self.grad_feat = torch.zeros(self.feat.numel(), dtype=torch.float32, device=self.device)
+        ws = _lib.scratch("ecorr_alt_backward_workspace_size", B, H, W, self.levels, self.radius, device=self.device,
+                          what=what)
+        _lib.check(_lib.lib().ecorr_alt_lookup_backward(
+            self.feat.data_ptr(), coords.data_ptr(), grad.data_ptr(), B, D, H, W, self.levels, self.radius,
+            self.grad_feat.data_ptr(), ws.data_ptr(), _lib.stream_of(grad)), what)
+
+
+class _PackFn(torch.autograd.Function):
+    """(fmap1, fmap2) -> one-element handle; the features themselves are a buffer of the block."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, state):
+        ctx.state = state
+        ctx.dtype = fmap1.dtype
+        return torch.zeros(1, dtype=torch.float32, device=state.device)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _grad_handle):
+        st = ctx.state
+        st.require_unconsumed()
+        st.consumed = True
+        B, D, H, W = st.shape
+        n1, n2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gf, st.grad_feat = st.grad_feat, None
+        with _lib.on_device(st.device):
+            if gf is None:   # no lookup received a gradient
+                z = [torch.zeros(st.shape, dtype=ctx.dtype, device=st.device) if n else None for n in (n1, n2)]
+                return z[0], z[1], None
+            g1 = torch.empty(st.shape, dtype=torch.float32, device=st.device) if n1 else None
+            g2 = torch.empty(st.shape, dtype=torch.float32, device=st.device) if n2 else None
+            _lib.check(_lib.lib().ecorr_alt_pack_backward(
+                gf.data_ptr(), B, D, H, W, st.levels, _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(gf)),
+                "AlternateCorrBlock pack backward")
+            if ctx.dtype != torch.float32:   # 16-bit fmaps: the fp32 result cast once
+                g1 = None if g1 is None else g1.to(ctx.dtype)
+                g2 = None if g2 is None else g2.to(ctx.dtype)
+        return g1, g2, None
+
+
+class _AltLookupFn(torch.autograd.Function):
+    """(handle, coords) -> the lookup; backward adds into the block's gradient feature buffer."""
+
+    @staticmethod
+    def forward(ctx, handle, coords, state, out_dtype):
+        ctx.state = state
+        ctx.save_for_backward(coords)   # versioned: an in-place change before backward raises
+        return _alt_lookup(state.feat, coords.contiguous(), state.shape, state.levels, state.radius, out_dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        st = ctx.state
+        st.require_unconsumed()
+        (coords,) = ctx.saved_tensors
+        go = grad_out.float().contiguous()   # a 16-bit lookup's gradient: the fp32 backward on its exact values
+        cc = coords.contiguous()
+        with _lib.on_device(st.device):
+            st.add_lookup_grad(go, cc)
+            return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None
+
+
+def _alt_lookup(feat, coords, shape, levels, radius, out_dtype):
+    """The ecorr_alt_lookup_as launch of the plain call and of _AltLookupFn.forward: contiguous, checked coords."""
+    B, D, H, W = shape
+    with _lib.on_device(feat.device):
+        out = torch.empty((B, _lib.corr_channels(levels, radius), H, W), dtype=out_dtype, device=feat.device)
+        _lib.check(_lib.lib().ecorr_alt_lookup_as(
+            feat.data_ptr(), coords.data_ptr(), B, D, H, W, levels, radius, out.data_ptr(),
+            _lib.OUT_FORMATS[out_dtype], _lib.stream_of(out)), "AlternateCorrBlock lookup")
+    return out
+
+
+class AlternateCorrBlock:
+    """Volume-free correlation lookup (module docstring); the interface of CorrBlock's forward.
+    trainable=True (keyword only): gradients for fmap1 / fmap2 through the lookups (module docstring)."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, fmap_dtype=None, differentiable=False,
+                 trainable=False):
         if differentiable:
-            raise NotImplementedError("AlternateCorrBlock is forward-only: differentiable=True needs a backward of "
-                                      "the on-the-fly lookup, which is not built (use CorrBlock)")
+            raise NotImplementedError("AlternateCorrBlock: differentiable=True is CorrBlock's keyword (a gradient "
+                                      "pyramid, which this block does not have); pass trainable=True for the "
+                                      "backward of the on-the-fly lookup")
         self.num_levels = num_levels
         self.radius = radius
         self._fmap_dtype = _lib.fmap_dtype_of(fmap_dtype)
-        _lib.require_fmap_pair(fmap1, fmap2, False, self._fmap_dtype)
+        live = _lib.require_fmap_pair(fmap1, fmap2, bool(trainable), self._fmap_dtype)
         if not (fmap1.is_contiguous() and fmap2.is_contiguous()):
             raise RuntimeError("fmap1/fmap2 must be contiguous (reference: view size is not "
                                "compatible with input tensor's size and stride)")
@@ -46,6 +167,10 @@ class AlternateCorrBlock:
         if B == 0 or D == 0 or H == 0 or W == 0:
             raise RuntimeError(f"AlternateCorrBlock: empty fmaps {tuple(fmap1.shape)} (B, D, H and W must be at "
                                "least 1: there is no volume to be NaN)")
+        if live and ((H >> (num_levels - 1)) < 2 or (W >> (num_levels - 1)) < 2):
+            raise RuntimeError(f"trainable AlternateCorrBlock: level {num_levels - 1} is "
+                               f"{H >> (num_levels - 1)} x {W >> (num_levels - 1)}; every level must be at least 2 x 2 "
+                               "(the reference's samples of a 1-pixel axis are NaN: division by size - 1 = 0)")
         self._shape = (B, D, H, W)
         self._device = fmap1.device
         what = "AlternateCorrBlock pack"
@@ -55,6 +180,10 @@ class AlternateCorrBlock:
             _lib.check(_lib.lib().ecorr_alt_pack_as(
                 fmap1.data_ptr(), fmap2.data_ptr(), _lib.ELEM_FORMATS[self._fmap_dtype], B, D, H, W, num_levels,
                 self._feat.data_ptr(), _lib.stream_of(self._feat)), what)
+        self._grad = self._handle = None
+        if live:
+            self._grad = _AltGradState(self._shape, num_levels, radius, self._feat, self._device)
+            self._handle = _PackFn.apply(fmap1, fmap2, self._grad)
 
     @property
     def corr_pyramid(self):
@@ -70,16 +199,16 @@ class AlternateCorrBlock:
         out_dtype = _lib.lookup_out_dtype(out_dtype)
         B, D, H, W = self._shape
         require_device("coords", coords)
-        no_grad_inputs(coords)
+        if self._grad is not None:
+            if torch.is_grad_enabled() and coords.requires_grad:
+                raise RuntimeError("trainable AlternateCorrBlock: coords requires grad; detach it (as eraft.py:127 "
+                                   "does), there is no gradient with respect to the coordinates")
+        else:
+            no_grad_inputs(coords)
         if tuple(coords.shape) != (B, 2, H, W):
             raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
         if coords.device != self._device:
             raise RuntimeError("coords is on a different device than the pyramid")
-        coords = coords.contiguous()
-        with _lib.on_device(self._device):
-            out = torch.empty((B, _lib.corr_channels(self.num_levels, self.radius), H, W), dtype=out_dtype,
-                              device=self._device)
-            _lib.check(_lib.lib().ecorr_alt_lookup_as(
-                self._feat.data_ptr(), coords.data_ptr(), B, D, H, W, self.num_levels, self.radius, out.data_ptr(),
-                _lib.OUT_FORMATS[out_dtype], _lib.stream_of(out)), "AlternateCorrBlock lookup")
-        return out
+        if self._grad is not None:
+            return _AltLookupFn.apply(self._handle, coords, self._grad, out_dtype)
+        return _alt_lookup(self._feat, coords.contiguous(), self._shape, self.num_levels, self.radius, out_dtype)

@@ -486,6 +486,14 @@ namespace {
 
 bool elem_format_ok(int f) { return f == ECORR_ELEM_F32 || f == ECORR_ELEM_F16 || f == ECORR_ELEM_BF16; }
 
+// the build's scale step (build_common): / sqrtf(D), a multiply where that is a power of two
+void alt_scale_of(int D, float* scale, int* is_mul) {
+    const float s = sqrtf((float)D);
+    int e = 0;
+    *is_mul = frexpf(s, &e) == 0.5f ? 1 : 0;
+    *scale = *is_mul ? 1.0f / s : s;
+}
+
 }  // namespace
 
 ECORR_EXPORT int ecorr_alt_size(int B, int D, int H, int W, int levels, int64_t* floats) {
@@ -528,12 +536,59 @@ ECORR_EXPORT int ecorr_alt_lookup_as(const float* feat, const float* coords, int
     P.levels = levels;
     P.radius = radius;
     P.C = levels * (2 * radius + 1) * (2 * radius + 1);
-    // the build's scale step (build_common): / sqrtf(D), a multiply where that is a power of two
-    const float s = sqrtf((float)D);
-    int e = 0;
-    P.scale_is_mul = frexpf(s, &e) == 0.5f ? 1 : 0;
-    P.scale = P.scale_is_mul ? 1.0f / s : s;
+    alt_scale_of(D, &P.scale, &P.scale_is_mul);
     return launch_alt_lookup(P, out_format, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_alt_backward_workspace_size(int B, int H, int W, int levels, int radius, int64_t* bytes) {
+    if (!bytes || radius < 0 || radius > 32) return ECORR_EINVAL;
+    AltGeom g;
+    const int st = alt_geometry(B, 1, H, W, levels, &g);   // the workspace does not depend on D
+    if (st != ECORR_OK) return st;
+    *bytes = alt_backward_workspace_bytes(B, (int64_t)H * W, levels, radius);
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_alt_lookup_backward(const float* feat, const float* coords, const float* grad_out, int B, int D,
+                                           int H, int W, int levels, int radius, float* grad_feat, void* workspace,
+                                           void* stream) {
+    if (!feat || !coords || !grad_out || !grad_feat || !workspace) return ECORR_EINVAL;
+    if (((uintptr_t)feat & 15) || ((uintptr_t)grad_feat & 15) || ((uintptr_t)workspace & 15)) return ECORR_EINVAL;
+    if (radius < 0 || radius > 32) return ECORR_EINVAL;
+    AltGeom g;
+    const int st = alt_geometry(B, D, H, W, levels, &g);
+    if (st != ECORR_OK) return st;
+    AltGradParams P{};
+    P.f1 = feat;
+    P.g1 = grad_feat;
+    for (int i = 0; i < levels; ++i) {
+        P.lvl[i] = feat + g.off[i];
+        P.glvl[i] = grad_feat + g.off[i];
+        P.lh[i] = g.h[i];
+        P.lw[i] = g.w[i];
+        P.lt0[i + 1] = P.lt0[i] + g.h[i] * g.w[i];
+    }
+    P.coords = coords;
+    P.grad_out = grad_out;
+    P.B = B;
+    P.Dp = g.Dp;
+    P.Q = H * W;
+    P.levels = levels;
+    P.radius = radius;
+    P.C = levels * (2 * radius + 1) * (2 * radius + 1);
+    P.org = static_cast<int2*>(workspace);
+    P.win = reinterpret_cast<float*>(P.org + (int64_t)B * levels * P.Q);
+    alt_scale_of(D, &P.scale, &P.scale_is_mul);
+    return launch_alt_lookup_backward(P, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_alt_pack_backward(float* grad_feat, int B, int D, int H, int W, int levels, float* grad_fmap1,
+                                         float* grad_fmap2, void* stream) {
+    if (!grad_feat || ((uintptr_t)grad_feat & 15)) return ECORR_EINVAL;
+    AltGeom g;
+    const int st = alt_geometry(B, D, H, W, levels, &g);
+    if (st != ECORR_OK) return st;
+    return launch_alt_pack_backward(grad_feat, B, D, H, W, g, grad_fmap1, grad_fmap2, (hipStream_t)stream);
 }
 
 ECORR_EXPORT int ecorr_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,

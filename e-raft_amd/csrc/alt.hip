@@ -33,10 +33,9 @@ __device__ __forceinline__ float alt_pool4(float a, float b, float c, float d) {
     return __fmul_rn(__fadd_rn(__fadd_rn(__fadd_rn(a, b), c), d), 0.25f);
 }
 
-// The build's scale step on a finished dot product (abi.hip build_common): / sqrtf(D), as a multiply
-// where sqrtf(D) is a power of two.
+// The build's scale step on a finished dot product (ecorr_device.h scale_step).
 __device__ __forceinline__ float alt_scale(const AltParams& P, float s) {
-    return P.scale_is_mul ? __fmul_rn(s, P.scale) : __fdiv_rn(s, P.scale);
+    return scale_step(P.scale_is_mul, P.scale, s);
 }
 
 // One output element at index i of out ([B][C][Q] order), fmt = ECORR_OUT_* (uniform).

@@ -106,6 +106,12 @@ __device__ __forceinline__ float unnormalize(float x, float size_m1, float half_
     return __fmul_rn(__fadd_rn(g, 1.0f), half_size_m1);
 }
 
+// The build's scale step on a finished sum (abi.hip build_common): / sqrtf(D), as a multiply where
+// sqrtf(D) is a power of two (scale is then 1 / sqrtf(D)).  The volume-free lookup and its backward.
+__device__ __forceinline__ float scale_step(int is_mul, float scale, float s) {
+    return is_mul ? __fmul_rn(s, scale) : __fdiv_rn(s, scale);
+}
+
 // One coordinate chain of the lookup (corr.py:41-43, utils.py:11-12, grid_sampler unnormalize): the
 // tap at offset d = o - r (o = 0 .. 2r) of the axis whose scaled coordinate is cs = coords / 2^lv, on
 // a level side of m1 + 1 pixels -> floor and fraction.  The forward (lookup_stage.h coord_chain<R>)

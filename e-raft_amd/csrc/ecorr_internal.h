@@ -217,6 +217,33 @@ int launch_alt_pack(const void* f1, const void* f2, int fmap_format, int B, int 
                     float* feat, hipStream_t stream);
 int launch_alt_lookup(const AltParams& P, int out_format, hipStream_t stream);
 
+// alt_grad.hip: the backward of the volume-free lookup (ecorr_alt_lookup_backward,
+// ecorr_alt_pack_backward).  The gradient feature buffer has the feature buffer's layout (AltGeom).
+// Workspace of one lookup backward, per (batch item, level, query): the window origin (two ints, x =
+// kAltNoWindow: the query has no window on that level) and, after all origins, its (2r+3)^2 window
+// gradient.
+constexpr int kAltNoWindow = INT32_MIN;
+int64_t alt_backward_workspace_bytes(int B, int64_t Q, int levels, int radius);
+struct AltGradParams {
+    const float* f1;                      // the features: [B][Q][Dp]
+    const float* lvl[ECORR_MAX_LEVELS];   // [B][h w][Dp]
+    float* g1;                            // their gradients, same layout
+    float* glvl[ECORR_MAX_LEVELS];
+    int lh[ECORR_MAX_LEVELS], lw[ECORR_MAX_LEVELS];
+    int lt0[ECORR_MAX_LEVELS + 1];        // first target pixel of each level in a batch item's list of all levels' pixels
+    const float* coords;                  // [B][2][Q]
+    const float* grad_out;                // [B][C][Q]
+    int2* org;                            // workspace: [B][levels][Q] origins
+    float* win;                           //            [B][levels][Q][(2r+3)^2] windows
+    int B, Dp, Q, levels, radius, C;
+    float scale;                          // the build's scale step (abi.hip build_common)
+    int scale_is_mul;
+};
+int launch_alt_lookup_backward(const AltGradParams& P, hipStream_t stream);
+// folds the pooled levels of grad_feat onto level 0, then transposes into the non-null outputs
+int launch_alt_pack_backward(float* grad_feat, int B, int D, int H, int W, const AltGeom& g, float* grad_fmap1,
+                             float* grad_fmap2, hipStream_t stream);
+
 int launch_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                             int Hg, int Wg, float* out, float* mask, hipStream_t stream);
 

@@ -16,6 +16,7 @@
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "lookup_grad_window.h"
 
 namespace ecorr {
 
@@ -26,14 +27,9 @@ constexpr int NT = 256;
 // ---------------------------------------------------------------------------------------------
 // lookup backward
 // ---------------------------------------------------------------------------------------------
-// The tap chains, the window fit and the in-range test are the forward's own (ecorr_device.h
-// coord_chain, window_fit, axis_in): the backward's support is the forward's by construction.
-//
-// LDS (floats), g = query of the block innermost so that lanes = queries never share a bank:
-//   cf / cw [K][QB]      floor (as float) and fraction of the current axis' K taps
-//   org     [3][QB]      window origin x, y and mode (0 window, 1 serial, 2 no query) as ints
-//   tmp     [K][S][QB]   x pass: row bb of the upstream summed into the S window columns
-//   win     [S][S][QB+1] the window gradient
+// Phases 0 - 2 (the tap chains, the window fit, the two separable passes into the LDS window) are
+// lookup_grad_window.h grad_window_phases, shared with the volume-free block's backward
+// (alt_grad.hip); its header describes the LDS carve.
 // RT >= 0: compile-time radius (the tuned r = 4), RT < 0: P.radius.
 template <int RT>
 __global__ __launch_bounds__(NT) void lookup_backward_kernel(LookupGradParams P, int QB) {
@@ -41,11 +37,9 @@ __global__ __launch_bounds__(NT) void lookup_backward_kernel(LookupGradParams P,
     const int r = RT >= 0 ? RT : P.radius;
     const int K = 2 * r + 1, S = K + 2, KK = K * K;
     const int QP = QB + 1;
-    float* cf = lds;
-    float* cw = cf + K * QB;
-    int* org = reinterpret_cast<int*>(cw + K * QB);
-    float* tmp = reinterpret_cast<float*>(org + 3 * QB);
-    float* win = tmp + K * S * QB;
+    const GradWindowLds L = grad_window_carve(lds, K, S, QB);
+    const int* org = L.org;
+    const float* win = L.win;
 
     const int tid = threadIdx.x;
     const int lv = blockIdx.y, b = blockIdx.z;
@@ -58,81 +52,7 @@ __global__ __launch_bounds__(NT) void lookup_backward_kernel(LookupGradParams P,
     const float* __restrict__ cyp = P.coords + ((int64_t)b * 2 + 1) * Q;
     const float* __restrict__ gout = P.grad_out + ((int64_t)b * P.C + (int64_t)lv * KK) * Q;
 
-    // ---- phase 0: the x chains, the window origin from the end taps of both axes, zeroed LDS
-    for (int i = tid; i < K * QB; i += NT) {
-        const int g = i % QB, o = i / QB;
-        float f = 0.0f, wg = 0.0f;
-        if (q0 + g < P.q_count) coord_chain(__fmul_rn(cxp[q0 + g], inv), o - r, wm1, f, wg);
-        cf[o * QB + g] = f;
-        cw[o * QB + g] = wg;
-    }
-    for (int g = tid; g < QB; g += NT) {
-        int md = 2, X0 = 0, Y0 = 0;
-        if (q0 + g < P.q_count) {
-            const float cx = __fmul_rn(cxp[q0 + g], inv), cy = __fmul_rn(cyp[q0 + g], inv);
-            float x0, xl, y0, yl, d;
-            coord_chain(cx, -r, wm1, x0, d);
-            coord_chain(cx, r, wm1, xl, d);
-            coord_chain(cy, -r, hm1, y0, d);
-            coord_chain(cy, r, hm1, yl, d);
-            const WindowFit f = window_fit(x0, xl, y0, yl, S - 2);
-            md = f.md, X0 = f.x0, Y0 = f.y0;   // md 1: the serial path
-        }
-        org[0 * QB + g] = X0;
-        org[1 * QB + g] = Y0;
-        org[2 * QB + g] = md;
-    }
-    for (int i = tid; i < K * S * QB; i += NT) tmp[i] = 0.0f;
-    for (int i = tid; i < S * S * QP; i += NT) win[i] = 0.0f;
-    __syncthreads();
-
-    // ---- phase 1 (x pass): thread = (query g, tap row bb); taps a = 0 .. K-1 in order:
-    //   tmp[bb][fx_a - X0] += (1 - wx_a) g[a][bb],  tmp[bb][fx_a + 1 - X0] += wx_a g[a][bb]
-    // for the corners whose x is inside the level.  Upstream reads: lanes = consecutive queries.
-    for (int i = tid; i < K * QB; i += NT) {
-        const int g = i % QB, bb = i / QB;
-        if (org[2 * QB + g] != 0) continue;
-        const int X0 = org[g];
-        float* row = tmp + (bb * S) * QB + g;
-        const float* gp = gout + q0 + g;
-#pragma unroll 3
-        for (int a = 0; a < K; ++a) {
-            const float go = gp[(int64_t)(a * K + bb) * Q];
-            const float f = cf[a * QB + g], wx = cw[a * QB + g];
-            const int ci = (int)f - X0;
-            if ((unsigned)ci > (unsigned)(S - 2)) continue;   // never: the end taps bound the window
-            if (axis_in(f, w)) row[ci * QB] = __fadd_rn(row[ci * QB], __fmul_rn(__fsub_rn(1.0f, wx), go));
-            if (axis_in(__fadd_rn(f, 1.0f), w))
-                row[(ci + 1) * QB] = __fadd_rn(row[(ci + 1) * QB], __fmul_rn(wx, go));
-        }
-    }
-    __syncthreads();
-    // ---- the y chains replace the x chains
-    for (int i = tid; i < K * QB; i += NT) {
-        const int g = i % QB, o = i / QB;
-        float f = 0.0f, wg = 0.0f;
-        if (q0 + g < P.q_count) coord_chain(__fmul_rn(cyp[q0 + g], inv), o - r, hm1, f, wg);
-        cf[o * QB + g] = f;
-        cw[o * QB + g] = wg;
-    }
-    __syncthreads();
-    // ---- phase 2 (y pass): thread = (query g, window column i); taps bb = 0 .. K-1 in order
-    for (int it = tid; it < S * QB; it += NT) {
-        const int g = it % QB, i = it / QB;
-        if (org[2 * QB + g] != 0) continue;
-        const int Y0 = org[QB + g];
-        float* col = win + i * QP + g;
-        for (int bb = 0; bb < K; ++bb) {
-            const float t = tmp[(bb * S + i) * QB + g];
-            const float f = cf[bb * QB + g], wy = cw[bb * QB + g];
-            const int ri = (int)f - Y0;
-            if ((unsigned)ri > (unsigned)(S - 2)) continue;
-            if (axis_in(f, h)) col[ri * S * QP] = __fadd_rn(col[ri * S * QP], __fmul_rn(__fsub_rn(1.0f, wy), t));
-            if (axis_in(__fadd_rn(f, 1.0f), h))
-                col[(ri + 1) * S * QP] = __fadd_rn(col[(ri + 1) * S * QP], __fmul_rn(wy, t));
-        }
-    }
-    __syncthreads();
+    grad_window_phases<NT>(L, cxp, cyp, gout, Q, P.q_count, q0, h, w, inv, r, QB);
 
     // ---- phase 3: G += window.  Each (query, pixel) has one thread; tiled / compact levels walk a
     // query's window row by row (lanes along x), interleaved levels put lanes on adjacent queries
@@ -366,16 +286,9 @@ __global__ __launch_bounds__(NT) void build_backward_kernel(BuildGradParams P) {
 
 }  // namespace
 
-// LDS floats of lookup_backward_kernel for QB queries at radius r
-static size_t lookup_backward_lds(int r, int QB) {
-    const size_t K = 2 * r + 1, S = K + 2;
-    return (2 * K * QB + 3 * QB + K * S * QB + S * S * (QB + 1)) * sizeof(float);
-}
-
 int launch_lookup_backward(const LookupGradParams& P, int B, hipStream_t stream) {
-    int QB = 64;   // as many queries per workgroup as fit 64 KB of LDS (64 at r <= 4, 1 at r = 32)
-    while (QB > 1 && lookup_backward_lds(P.radius, QB) > 64 * 1024) QB >>= 1;
-    const size_t lds = lookup_backward_lds(P.radius, QB);
+    const int QB = grad_window_queries(P.radius);
+    const size_t lds = grad_window_lds_bytes(P.radius, QB);
     const dim3 grid((unsigned)((P.q_count + QB - 1) / QB), (unsigned)P.levels, (unsigned)B);
     if (P.radius == 4) hipLaunchKernelGGL((lookup_backward_kernel<4>), grid, dim3(NT), lds, stream, P, QB);
     else hipLaunchKernelGGL((lookup_backward_kernel<-1>), grid, dim3(NT), lds, stream, P, QB);

@@ -214,6 +214,11 @@ class ERAFT(nn.Module):
     more time.  It composes with mixed_precision (16-bit fmaps in, 16-bit lookup out) and hip_upsample; it
     is forward-only and has no fused convc1, so fuse_motion_corr, train_motion_corr and
     differentiable_corr raise ValueError with it.
+    train_alternate_corr=True (keyword only; named after train_motion_corr) is alternate_corr on a trainable
+    AlternateCorrBlock (trainable=True; csrc/alt_grad.hip): a loss on the predictions trains
+    fnet through the volume-free lookup's HIP backward, without a pyramid or a gradient pyramid.  It implies
+    alternate_corr=True, combines with mixed_precision and hip_upsample as alternate_corr does, and raises
+    ValueError with fuse_motion_corr, train_motion_corr or differentiable_corr.
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
@@ -221,8 +226,15 @@ class ERAFT(nn.Module):
 
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
                  differentiable_corr=False, train_motion_corr=False, mixed_precision=False,
-                 amp_dtype=torch.float16, _native_half_lookup=True, *, alternate_corr=False):
+                 amp_dtype=torch.float16, _native_half_lookup=True, *, alternate_corr=False,
+                 train_alternate_corr=False):
         super().__init__()
+        if train_alternate_corr and (fuse_motion_corr or train_motion_corr or differentiable_corr):
+            raise ValueError("train_alternate_corr=True cannot be combined with fuse_motion_corr, train_motion_corr or "
+                             "differentiable_corr: it trains through AlternateCorrBlock(trainable=True), which has no "
+                             "volume, no gradient pyramid and no fused convc1")
+        self.train_alternate_corr = bool(train_alternate_corr)
+        alternate_corr = alternate_corr or self.train_alternate_corr
         if alternate_corr and (fuse_motion_corr or train_motion_corr or differentiable_corr):
             raise ValueError("alternate_corr=True cannot be combined with fuse_motion_corr, train_motion_corr or "
                              "differentiable_corr: AlternateCorrBlock is forward-only and has no fused convc1")
@@ -292,6 +304,8 @@ class ERAFT(nn.Module):
         # differentiable_corr: gradients reach fnet through the HIP backward (corr.py); the keywords
         # are passed only on their paths, so a reference-signature CorrBlock can stand in otherwise
         kw = {"differentiable": True} if self.differentiable_corr else {}
+        if self.train_alternate_corr:
+            kw = {"trainable": True}
         block = AlternateCorrBlock if self.alternate_corr else CorrBlock   # the volume-free lookup, or the pyramid
         if half_lookup and fmap1.dtype == self.amp_dtype and fmap2.dtype == self.amp_dtype:
             corr_fn = block(fmap1.contiguous(), fmap2.contiguous(), num_levels=self.corr_levels,

@@ -456,6 +456,31 @@ int ecorr_alt_pack_as(const void* fmap1, const void* fmap2, int fmap_format, int
 int ecorr_alt_lookup_as(const float* feat, const float* coords, int B, int D, int H, int W, int levels,
                         int radius, void* out, int out_format, void* stream);
 
+/* The backward of the volume-free lookup (three more entries added within ABI 17, csrc/alt_grad.hip):
+ * the gradients of the two fmaps without a gradient pyramid.  With s = 1/sqrt(D), F2_i the pooled fmap2
+ * level i and Wg_i[p] the (2r+3)^2 window gradient of query p on level i (ecorr_lookup_backward's window:
+ * the same device function), grad_f1[p,:] = s sum_i sum_t Wg_i[p][t] F2_i[t,:], grad_F2_i[t,:] = s sum_p
+ * Wg_i[p][t] f1[p,:], and grad_fmap2 is the fold of the grad_F2_i onto level 0 (the chain of floor-mode
+ * avg_pool2d backwards).  No atomics: the destination owns every sum and each runs in a fixed order,
+ * so equal inputs give bitwise equal gradients.  Queries with NaN / inf / huge coordinates contribute
+ * nothing.  First order only; there is no gradient with respect to coords.
+ * grad_feat: ecorr_alt_size floats in the feature buffer's layout, 16-byte aligned.  Workspace:
+ * ecorr_alt_backward_workspace_size bytes, 16-byte aligned -- per (batch item, level, query) two ints of
+ * window origin and (2r+3)^2 floats of window, B*levels*H*W*(8 + 4 (2r+3)^2) bytes; it needs no
+ * initialisation.  Radius 0 .. 32 (the forward window kernel's 128-tap limit does not apply).
+ * Errors (before any GPU call), all ECORR_EINVAL: those of ecorr_alt_lookup_as, and a null or misaligned
+ * grad_feat or workspace. */
+int ecorr_alt_backward_workspace_size(int B, int H, int W, int levels, int radius, int64_t* bytes);
+/* grad_feat += one lookup's contribution (grad_feat: ecorr_alt_size floats in the feature buffer's layout,
+ * zeroed by the caller before the block's first call; calls on one grad_feat stream-ordered).
+ * grad_out float[B][levels*(2r+1)^2][H*W].  workspace: contents undefined before and after. */
+int ecorr_alt_lookup_backward(const float* feat, const float* coords, const float* grad_out, int B, int D,
+                              int H, int W, int levels, int radius, float* grad_feat, void* workspace, void* stream);
+/* Consumes grad_feat (the pooled fmap2 levels are folded onto level 0 in place).
+ * grad_fmap1 / grad_fmap2 float[B][D][H][W]; either may be NULL. */
+int ecorr_alt_pack_backward(float* grad_feat, int B, int D, int H, int W, int levels,
+                            float* grad_fmap1, float* grad_fmap2, void* stream);
+
 /* Tile shape of the pyramid storage (ECORR_TILE_H, ECORR_TILE_W). */
 int ecorr_pyramid_tile(int* tile_h, int* tile_w);
 

@@ -14,6 +14,7 @@
 #include <vector>
 #include <algorithm>
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
+struct int2 { int x, y; };   // ecorr_internal.h names it (the volume-free backward's workspace origins)
 inline thread_local dim3 threadIdx;
 inline dim3 blockIdx, gridDim;
 inline std::barrier<>* g_bar;
