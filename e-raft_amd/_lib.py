@@ -120,6 +120,13 @@ SYMBOLS = {
     "ecorr_conv1x1_split_pack_presplit": (_i, [_p, _i, _i, _p, _p]),
     # (in, B, levels, Q, scale, packed, bias, O, out, stream)
     "ecorr_conv1x1_relu_presplit": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
+    # SepConvGRU (added within ABI 17): (hidden, input, bytes*) /
+    # (weight[6], bias[6], hidden, input, packed, stream) / (B, hidden, input, H, W, bytes*) /
+    # (h, x, B, hidden, input, H, W, packed, h_out, workspace, stream)
+    "ecorr_sepconv_gru_packed_size": (_i, [_i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_sepconv_gru_pack": (_i, [ctypes.POINTER(_p), ctypes.POINTER(_p), _i, _i, _p, _p]),
+    "ecorr_sepconv_gru_workspace_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_sepconv_gru": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ecorr_bilinear_sampler": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
     "ecorr_coords_grid": (_i, [_i, _i, _i, _p, _p]),
     # (chunks, chunk, world, B, C, H, W, out, stream)
@@ -210,9 +217,9 @@ def require_device(name, t, dtype=torch.float32):
         raise TypeError(f"{name} must be {str(dtype).removeprefix('torch.')} (got {t.dtype})")
 
 
-def no_grad_inputs(*ts):
+def no_grad_inputs(*ts, what="CorrBlock"):
     if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
-        raise RuntimeError("eraft_amd CorrBlock is forward-only; call it under torch.no_grad() "
+        raise RuntimeError(f"eraft_amd {what} is forward-only; call it under torch.no_grad() "
                            "(as the reference harness does, test.py:80)")
 
 

@@ -591,6 +591,46 @@ ECORR_EXPORT int ecorr_alt_pack_backward(float* grad_feat, int B, int D, int H, 
     return launch_alt_pack_backward(grad_feat, B, D, H, W, g, grad_fmap1, grad_fmap2, (hipStream_t)stream);
 }
 
+ECORR_EXPORT int ecorr_sepconv_gru_packed_size(int hidden, int input, int64_t* bytes) {
+    if (!bytes || !gru_sizes_ok(hidden, input)) return ECORR_EINVAL;
+    *bytes = gru_packed_bytes();
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_sepconv_gru_pack(const float* const weight[6], const float* const bias[6], int hidden,
+                                        int input, void* packed, void* stream) {
+    if (!weight || !bias || !packed || ((uintptr_t)packed & 15) || !gru_sizes_ok(hidden, input)) return ECORR_EINVAL;
+    for (int i = 0; i < 6; ++i)
+        if (!weight[i] || !bias[i]) return ECORR_EINVAL;
+    return launch_gru_pack(weight, bias, packed, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_sepconv_gru_workspace_size(int B, int hidden, int input, int H, int W, int64_t* bytes) {
+    if (!bytes || !gru_sizes_ok(hidden, input) || !gru_geometry_ok(B, H, W)) return ECORR_EINVAL;
+    *bytes = gru_workspace_bytes(B, H, W);
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_sepconv_gru(const float* h, const float* x, int B, int hidden, int input, int H, int W,
+                                   const void* packed, float* h_out, void* workspace, void* stream) {
+    if (!h || !x || !packed || !h_out || !workspace || !gru_sizes_ok(hidden, input) || !gru_geometry_ok(B, H, W))
+        return ECORR_EINVAL;
+    if (((uintptr_t)packed & 15) || ((uintptr_t)workspace & 15)) return ECORR_EINVAL;
+    // h_out overlapping h or x: the second half-step's taps would read what it is writing; the workspace
+    // overlapping any of the three: a launch would write h1, z or r*h over what it (or the next) reads
+    const uintptr_t n = (uintptr_t)B * H * W * 4;
+    auto overlap = [](const void* a, uintptr_t na, const void* b, uintptr_t nb) {
+        return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+    };
+    const uintptr_t nws = (uintptr_t)gru_workspace_bytes(B, H, W);
+    if (overlap(h_out, n * hidden, h, n * hidden) || overlap(h_out, n * hidden, x, n * input) ||
+        overlap(workspace, nws, h, n * hidden) || overlap(workspace, nws, x, n * input) ||
+        overlap(workspace, nws, h_out, n * hidden) || overlap(packed, (uintptr_t)gru_packed_bytes(), workspace, nws) ||
+        overlap(packed, (uintptr_t)gru_packed_bytes(), h_out, n * hidden))
+        return ECORR_EINVAL;
+    return launch_gru(h, x, B, H, W, packed, h_out, workspace, (hipStream_t)stream);
+}
+
 ECORR_EXPORT int ecorr_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                                         int Hg, int Wg, float* out, float* mask, void* stream) {
     if (!img || !coords || !out || N <= 0 || C < 0 || h <= 0 || w <= 0 || Hg <= 0 || Wg <= 0)

@@ -244,6 +244,16 @@ int launch_alt_lookup_backward(const AltGradParams& P, hipStream_t stream);
 int launch_alt_pack_backward(float* grad_feat, int B, int D, int H, int W, const AltGeom& g, float* grad_fmap1,
                              float* grad_fmap2, hipStream_t stream);
 
+// gru.hip: SepConvGRU (ecorr_sepconv_gru*, include/ecorr.h).  gru_sizes_ok: the (hidden, input) the kernels
+// are built for; gru_geometry_ok: B, H, W within their 32-bit offsets and grid limits.
+bool gru_sizes_ok(int hidden, int input);
+bool gru_geometry_ok(int B, int H, int W);
+int64_t gru_packed_bytes();
+int64_t gru_workspace_bytes(int B, int H, int W);
+int launch_gru_pack(const float* const weight[6], const float* const bias[6], void* packed, hipStream_t stream);
+int launch_gru(const float* h, const float* x, int B, int H, int W, const void* packed, float* h_out, void* workspace,
+               hipStream_t stream);
+
 int launch_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                             int Hg, int Wg, float* out, float* mask, hipStream_t stream);
 

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 from .alt_corr import AlternateCorrBlock
 from .corr import CorrBlock
 from .flow import upsample_flow as hip_upsample_flow
+from .gru import sepconv_gru
 from .utils import coords_grid
 
 
@@ -147,8 +148,9 @@ class FlowHead(nn.Module):
 
 
 class BasicUpdateBlock(nn.Module):
-    def __init__(self, hidden_dim=128, corr_levels=4, corr_radius=4):
+    def __init__(self, hidden_dim=128, corr_levels=4, corr_radius=4, hip_gru=False):
         super().__init__()
+        self.hip_gru = bool(hip_gru)   # the GRU as eraft_amd.sepconv_gru on self.gru's weights (same keys)
         self.encoder = BasicMotionEncoder(corr_levels, corr_radius)
         self.gru = SepConvGRU(hidden_dim=hidden_dim, input_dim=128 + hidden_dim)
         self.flow_head = FlowHead(hidden_dim, hidden_dim=256)
@@ -157,7 +159,7 @@ class BasicUpdateBlock(nn.Module):
 
     def forward(self, net, inp, corr, flow, corr_is_convc1=False):
         inp = torch.cat([inp, self.encoder(flow, corr, corr_is_convc1)], dim=1)
-        net = self.gru(net, inp)
+        net = sepconv_gru(net.contiguous(), inp, self.gru) if self.hip_gru else self.gru(net, inp)
         return net, 0.25 * self.mask(net), self.flow_head(net)
 
 
@@ -219,6 +221,10 @@ class ERAFT(nn.Module):
     fnet through the volume-free lookup's HIP backward, without a pyramid or a gradient pyramid.  It implies
     alternate_corr=True, combines with mixed_precision and hip_upsample as alternate_corr does, and raises
     ValueError with fuse_motion_corr, train_motion_corr or differentiable_corr.
+    hip_gru=True (keyword only) runs the update block's SepConvGRU as eraft_amd.sepconv_gru (csrc/gru.hip,
+    DESIGN.md §3.11) on the same parameters (the state_dict keys are unchanged): fp32 and forward-only.  It
+    composes with fuse_motion_corr, hip_upsample and alternate_corr, and raises ValueError with
+    mixed_precision, differentiable_corr, train_motion_corr or train_alternate_corr.
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
@@ -227,8 +233,12 @@ class ERAFT(nn.Module):
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
                  differentiable_corr=False, train_motion_corr=False, mixed_precision=False,
                  amp_dtype=torch.float16, _native_half_lookup=True, *, alternate_corr=False,
-                 train_alternate_corr=False):
+                 train_alternate_corr=False, hip_gru=False):
         super().__init__()
+        if hip_gru and (mixed_precision or differentiable_corr or train_motion_corr or train_alternate_corr):
+            raise ValueError("hip_gru=True cannot be combined with mixed_precision, differentiable_corr, "
+                             "train_motion_corr or train_alternate_corr: the HIP SepConvGRU is fp32 and forward-only")
+        self.hip_gru = bool(hip_gru)
         if train_alternate_corr and (fuse_motion_corr or train_motion_corr or differentiable_corr):
             raise ValueError("train_alternate_corr=True cannot be combined with fuse_motion_corr, train_motion_corr or "
                              "differentiable_corr: it trains through AlternateCorrBlock(trainable=True), which has no "
@@ -263,7 +273,8 @@ class ERAFT(nn.Module):
                                  n_first_channels=n_first_channels)
         self.cnet = BasicEncoder(output_dim=self.hidden_dim + self.context_dim, norm_fn="batch",
                                  dropout=0, n_first_channels=n_first_channels)
-        self.update_block = BasicUpdateBlock(self.hidden_dim, self.corr_levels, self.corr_radius)
+        self.update_block = BasicUpdateBlock(self.hidden_dim, self.corr_levels, self.corr_radius,
+                                             hip_gru=self.hip_gru)
 
     def freeze_bn(self):
         """Keep every BatchNorm2d on its running statistics while the rest trains (eraft.py:60-63)."""

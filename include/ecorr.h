@@ -481,6 +481,42 @@ int ecorr_alt_lookup_backward(const float* feat, const float* coords, const floa
 int ecorr_alt_pack_backward(float* grad_feat, int B, int D, int H, int W, int levels,
                             float* grad_fmap1, float* grad_fmap2, void* stream);
 
+/* ---- SepConvGRU (four entries added within ABI 17: purely additive, the version stays 17) ----
+ * The update block's separable ConvGRU (model/update.py:33-60, csrc/gru.hip): a half-step along x with
+ * the (1,5) convolutions z1 r1 q1, then one along y with the (5,1) convolutions z2 r2 q2, zero padding 2:
+ *   z = sigmoid(conv_z([h, x])), r = sigmoid(conv_r([h, x])), q = tanh(conv_q([r*h, x])), h' = (1-z)*h + z*q.
+ * h float[B][hidden][H][W], x float[B][input][H][W], h_out float[B][hidden][H][W], contiguous fp32; h and x
+ * are read in place (no concatenation).  Supported sizes: hidden = 128 and input = 256 only (the update
+ * block's); every other (hidden, input) returns ECORR_EINVAL from all four entries.  H = 1 and W = 1 are
+ * valid (every off-centre tap is then padding).  Forward only.
+ * Arithmetic: the products run on the fp32 matrix instruction (exact fp32 operands, fp32 accumulation in
+ * chains of 192 products that are then summed), sigmoid as 1 / (1 + expf(-v)), tanhf, the blend as two
+ * products and a sum: within 1e-5 of an fp64 GRU, normwise (max |error| / rms).  No atomics: bitwise
+ * reproducible.  Non-finite values: a NaN in h or x makes the outputs of its own batch item NaN on
+ * exactly the reference's footprint (the 9 x 9 block around the pixel, clipped to the image, all channels:
+ * two taps per half-step, and two more because r*h carries it into q's taps) and nowhere else -- there is
+ * no shared exponent to spread it; +-inf behaves as in an fp32
+ * convolution (inf * 0 weight = NaN; no split, so no inf - inf of the split kernels).
+ * Packed weights: ecorr_sepconv_gru_packed_size bytes = 4 * (6 * hidden * (hidden + input) * 5 + 6 * hidden),
+ * 16-byte aligned; written once per weight set by ecorr_sepconv_gru_pack (one launch) from weight[i]
+ * float[hidden][hidden + input][5] and bias[i] float[hidden], i in the order z1 r1 q1 z2 r2 q2 (a (1,5)
+ * and a (5,1) kernel both flatten to that).  The arrays of six pointers are host arrays of device pointers.
+ * Workspace: ecorr_sepconv_gru_workspace_size bytes = 3 * B * hidden * H * W * 4 (the first half-step's h,
+ * z and r*h), 16-byte aligned; it needs no initialisation and its contents are undefined afterwards.
+ * ecorr_sepconv_gru: four launches on `stream`, no host synchronisation, no allocation.
+ * Errors (before any GPU call), all ECORR_EINVAL: a null pointer (an array entry included), an unsupported
+ * (hidden, input), B, H or W < 1, B > 65535, B * (hidden + input) * H * W * 4 beyond 2^31 - 1 (the buffer
+ * range of the kernels' 32-bit offsets), a packed buffer or workspace that is not 16-byte aligned, h_out
+ * overlapping h or x, and the workspace overlapping h, x or h_out, or the packed buffer overlapping the
+ * workspace or h_out: the five buffers must be disjoint, except that h and x are only read and may share
+ * memory with each other or with the pack. */
+int ecorr_sepconv_gru_packed_size(int hidden, int input, int64_t* bytes);
+int ecorr_sepconv_gru_pack(const float* const weight[6], const float* const bias[6],
+                           int hidden, int input, void* packed, void* stream);
+int ecorr_sepconv_gru_workspace_size(int B, int hidden, int input, int H, int W, int64_t* bytes);
+int ecorr_sepconv_gru(const float* h, const float* x, int B, int hidden, int input, int H, int W,
+                      const void* packed, float* h_out, void* workspace, void* stream);
+
 /* Tile shape of the pyramid storage (ECORR_TILE_H, ECORR_TILE_W). */
 int ecorr_pyramid_tile(int* tile_h, int* tile_w);
 
