@@ -692,6 +692,7 @@ bool upsample_dims_ok(int N, int H, int W) {
 ECORR_EXPORT int ecorr_upsample_flow(const float* flow, const float* mask, int N, int H, int W, float* out,
                                      void* stream) {
     if (!flow || !mask || !out || !upsample_dims_ok(N, H, W)) return ECORR_EINVAL;
+    if ((uintptr_t)out & 15) return ECORR_EINVAL;   // upsample_kernel stores out as 16-byte vectors
     return launch_upsample_flow(flow, mask, N, H, W, out, (hipStream_t)stream);
 }
 
@@ -706,6 +707,7 @@ ECORR_EXPORT int ecorr_upsample_flow_backward(const float* grad_out, const float
                                               void* stream) {
     if (!grad_out || !flow || !mask || (!grad_flow && !grad_mask) || !upsample_dims_ok(N, H, W)) return ECORR_EINVAL;
     if (!workspace && upsample_backward_workspace_bytes(N, H, W) > 0) return ECORR_EINVAL;
+    if ((uintptr_t)grad_out & 15) return ECORR_EINVAL;   // upsample_backward_kernel loads grad_out as 16-byte vectors
     return launch_upsample_flow_backward(grad_out, flow, mask, N, H, W, grad_flow, grad_mask, workspace,
                                          (hipStream_t)stream);
 }

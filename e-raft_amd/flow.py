@@ -15,11 +15,19 @@ from . import _lib
 from ._lib import require_device
 
 
+def _aligned16(t):
+    """t (contiguous) at a 16-byte aligned address: itself, or a copy where it is a view at a storage
+    offset that is no multiple of 4 floats.  The kernels access out and grad_out as 16-byte vectors and
+    the C ABI refuses a misaligned one (ECORR_EINVAL).  The forward's out is allocated here, so aligned;
+    a caller-visible output, if one is ever passed in, needs the same treatment."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _upsample(flow, mask):
     """The ecorr_upsample_flow launch on contiguous flow [N, 2, H, W] and mask (N * 576 * H * W elements)."""
     N, _, H, W = flow.shape
     with _lib.on_device(flow.device):
-        out = torch.empty((N, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
+        out = torch.empty((N, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)   # the allocator aligns it
         _lib.check(_lib.lib().ecorr_upsample_flow(flow.data_ptr(), mask.data_ptr(), N, H, W, out.data_ptr(),
                                                   _lib.stream_of(flow)), "upsample_flow")
     return out
@@ -39,7 +47,7 @@ class _UpsampleFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         flow, mask = ctx.saved_tensors
         N, _, H, W = flow.shape
-        go = grad_out.contiguous()   # ImagePadder.unpad: the gradient of a slice
+        go = _aligned16(grad_out.contiguous())   # ImagePadder.unpad: the gradient of a slice
         fc, mc = flow.contiguous(), mask.contiguous()
         need_flow, need_mask = ctx.needs_input_grad
         with _lib.on_device(fc.device):

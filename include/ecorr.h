@@ -376,6 +376,16 @@ int ecorr_grid_sample_values(const float* pts, int64_t n, int h, int w, float* v
 /* ERAFT.upsample_flow: flow float[N][2][H][W], mask float[N][576][H][W] (the update block's
  * 0.25 * mask head) -> out float[N][2][8H][8W]; softmax over the 9 taps, convex combination of
  * the zero-padded 3x3 window of 8 * flow.  Within a few ulp of the reference (device expf).
+ * out must be 16-byte aligned (it is stored as 16-byte vectors; every row of it then is, 8W floats
+ * long); flow and mask need a float's alignment only.  A misaligned out is ECORR_EINVAL, as null
+ * pointers and N, H, W outside N <= 65535, H * W <= 2^26 are, before any launch.
+ * Non-finite values keep the reference's footprint.  A NaN in flow[n][c][y][x] makes channel c NaN on
+ * the 8x8 blocks of the pixels of its 3x3 neighbourhood inside the map (a weight times NaN), and +-inf
+ * there gives +-inf on those blocks, NaN where +inf and -inf meet or a weight is 0; the other channel,
+ * the other items and every other pixel keep the bits of the finite run.  A sub-pixel whose nine logits
+ * hold a NaN, a +inf, or nothing but -inf has both its outputs (c = 0, 1) NaN and touches nothing else
+ * (the maximum is taken with fmaxf, which drops a NaN, and the NaN returns through the sum); a -inf
+ * logit beside finite ones is a weight of exactly 0.
  * Replaces: model/eraft.py:74-85. */
 int ecorr_upsample_flow(const float* flow, const float* mask, int N, int H, int W, float* out, void* stream);
 
@@ -389,7 +399,8 @@ int ecorr_upsample_flow(const float* flow, const float* mask, int N, int H, int 
  * equal inputs give bitwise equal gradients.  workspace: ecorr_upsample_backward_workspace_size bytes
  * of device memory (float[N][18][H*W], contents undefined before and after), required whichever
  * gradients are asked for; NULL is ECORR_EINVAL.  N, H, W as ecorr_upsample_flow (N <= 65535,
- * H * W <= 2^26, any H, W >= 1); validation happens before any launch.
+ * H * W <= 2^26, any H, W >= 1).  grad_out must be 16-byte aligned (it is read as 16-byte vectors);
+ * a misaligned grad_out is ECORR_EINVAL.  Validation happens before any launch.
  * Replaces: autograd of eraft.py:74-85. */
 int ecorr_upsample_backward_workspace_size(int N, int H, int W, int64_t* bytes);
 int ecorr_upsample_flow_backward(const float* grad_out, const float* flow, const float* mask, int N, int H, int W,

@@ -5,6 +5,7 @@ bit pattern, GUARD floats of it on each side: a store outside the output changes
 element the kernel never wrote keeps the pattern.
 guarded_u8 / check_guarded_u8: the same for a byte output (the splat's valid mask), BYTE_FILL = 0x7b being
 neither 0 nor 1.
+guarded_u16 / check_guarded_u16: a uint16 output in the middle of a guarded_u8 buffer (the PNG codec's).
 Workspace: a kernel's byte scratch of exactly the size its size entry reports, WS_GUARD bytes of guard
 on each side, everything prefilled with a byte the caller chooses; a zero-byte one is passed as NULL.
 mismatch: the text of a failed bitwise comparison.
@@ -54,6 +55,23 @@ def check_guarded_u8(buf, what):
     left = int((mid == BYTE_FILL).sum())
     assert left == 0, f"{what}: {left} of {mid.size} bytes were never written"
     return mid
+
+
+def guarded_u16(n, device="cuda"):
+    """(the whole uint8 buffer of guarded_u8(2 n), its middle as n uint16), BYTE_FILL everywhere."""
+    import torch
+    buf, mid = guarded_u8(2 * n, device)
+    return buf, mid.view(torch.uint16)
+
+
+def check_guarded_u16(buf, what):
+    """Asserts the guards of a guarded_u16 buffer untouched -> the middle as numpy uint16.  A written
+    element may be 0x7b7b itself (the DSEC codec's channels span the whole range), so what was never
+    written shows in the caller's comparison of every element, not here."""
+    host = buf.cpu().numpy()
+    G = 4 * GUARD
+    assert (host[:G] == BYTE_FILL).all() and (host[-G:] == BYTE_FILL).all(), f"{what}: a guard band was written"
+    return host[G:-G].view(np.uint16)
 
 
 class Workspace:

@@ -64,20 +64,20 @@ def test_backward_validation(ea):
     # (grad_out, flow, mask, N, H, W, grad_flow, grad_mask, workspace, stream)
     F = ea.lib().ecorr_upsample_flow_backward
     assert F(None, 8, 8, 1, 4, 4, 8, 8, 8, None) == EINVAL
-    assert F(8, None, 8, 1, 4, 4, 8, 8, 8, None) == EINVAL
-    assert F(8, 8, None, 1, 4, 4, 8, 8, 8, None) == EINVAL
-    assert F(8, 8, 8, 1, 4, 4, None, None, 8, None) == EINVAL      # both gradients NULL
-    assert F(8, 8, 8, 0, 4, 4, 8, 8, 8, None) == EINVAL
-    assert F(8, 8, 8, 65536, 4, 4, 8, 8, 8, None) == EINVAL
-    assert F(8, 8, 8, 1, 0, 4, 8, 8, 8, None) == EINVAL
-    assert F(8, 8, 8, 1, 4, 0, 8, 8, 8, None) == EINVAL
-    assert F(8, 8, 8, 1, 8193, 8192, 8, 8, 8, None) == EINVAL      # H * W > 2^26
+    assert F(16, None, 8, 1, 4, 4, 8, 8, 8, None) == EINVAL
+    assert F(16, 8, None, 1, 4, 4, 8, 8, 8, None) == EINVAL
+    assert F(16, 8, 8, 1, 4, 4, None, None, 8, None) == EINVAL      # both gradients NULL
+    assert F(16, 8, 8, 0, 4, 4, 8, 8, 8, None) == EINVAL
+    assert F(16, 8, 8, 65536, 4, 4, 8, 8, 8, None) == EINVAL
+    assert F(16, 8, 8, 1, 0, 4, 8, 8, 8, None) == EINVAL
+    assert F(16, 8, 8, 1, 4, 0, 8, 8, 8, None) == EINVAL
+    assert F(16, 8, 8, 1, 8193, 8192, 8, 8, 8, None) == EINVAL      # H * W > 2^26
     # NULL workspace where the size query is positive, whichever gradients are asked for
     assert _size(ea, 1, 4, 4)[1] > 0
-    assert F(8, 8, 8, 1, 4, 4, 8, 8, None, None) == EINVAL
-    assert F(8, 8, 8, 1, 4, 4, 8, None, None, None) == EINVAL
-    assert F(8, 8, 8, 1, 4, 4, None, 8, None, None) == EINVAL
+    assert F(16, 8, 8, 1, 4, 4, 8, 8, None, None) == EINVAL
+    assert F(16, 8, 8, 1, 4, 4, 8, None, None, None) == EINVAL
+    assert F(16, 8, 8, 1, 4, 4, None, 8, None, None) == EINVAL
     # the same codes as the forward for the same geometry
     U = ea.lib().ecorr_upsample_flow   # (flow, mask, N, H, W, out, stream)
     for N, H, W in [(0, 4, 4), (65536, 4, 4), (1, 0, 4), (1, 4, 0), (1, 8193, 8192)]:
-        assert U(8, 8, N, H, W, 8, None) == F(8, 8, 8, N, H, W, 8, 8, 8, None) == EINVAL
+        assert U(8, 8, N, H, W, 16, None) == F(16, 8, 8, N, H, W, 8, 8, 8, None) == EINVAL
