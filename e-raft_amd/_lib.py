@@ -223,6 +223,24 @@ def no_grad_inputs(*ts, what="CorrBlock"):
                            "(as the reference harness does, test.py:80)")
 
 
+def check_coords(coords, shape, device, train=False, who=None, rows=False):
+    """The coords check of every block's lookup: a float32 HIP tensor of `shape` on the pyramid's `device`.
+    train: the call goes through autograd (coords that require grad are refused in the name of `who`, before
+    the shape is looked at), else it is forward-only.  rows: the shape text of RowShardedCorrBlock's slab."""
+    require_device("coords", coords)
+    if train:
+        if torch.is_grad_enabled() and coords.requires_grad:
+            raise RuntimeError(f"{who}: coords requires grad; detach it (as eraft.py:127 does), "
+                               "there is no gradient with respect to the coordinates")
+    else:
+        no_grad_inputs(coords)
+    if tuple(coords.shape) != shape:
+        raise RuntimeError(f"coords rows {tuple(coords.shape)} != {shape}" if rows else
+                           f"coords shape {tuple(coords.shape)} != {shape} of the pyramid")
+    if coords.device != device:
+        raise RuntimeError("coords is on a different device than the pyramid")
+
+
 def fmap_dtype_of(fmap_dtype):
     """The dtype both fmaps must have for the fmap_dtype argument of CorrBlock: None = float32."""
     if fmap_dtype is None:

@@ -32,12 +32,9 @@ buffer and, during a lookup's backward, a workspace of the queries' window gradi
 is CorrBlock's: the gradient path is live when trainable is set, grad mode is on and an fmap requires
 grad; otherwise the block is the plain block (and without trainable, fmaps that require grad still
 raise "forward-only").  The forward of a live block runs the same launches, so its values are bitwise
-the plain block's.  Autograd structure as corr.py's: the pack is a Function of the fmaps returning a
-one-element handle, each lookup a Function of (handle, coords) that saves only coords and whose
-backward adds its contribution into the block's gradient feature buffer (allocated and zeroed on the
-first one) and returns a zero for the handle; the pack's backward then runs once, after all of them,
-turns the buffer into the two fmap gradients and frees it.  The backward reads the block's own fp32
-copy of the features, so no fmap is saved and an in-place change of an fmap after construction does
+the plain block's.  Autograd structure as CorrBlock's (the handle mechanism of _grad.py), with the
+gradient feature buffer in the gradient pyramid's place and each lookup saving only coords.  The
+backward reads the block's own fp32 copy of the features, so no fmap is saved and an in-place change of an fmap after construction does
 not affect (or invalidate) the backward: the gradients are those of the values the block was built
 from.  Deterministic (no atomics).  Contract of the live block, as the differentiable CorrBlock's:
 coords are detached (coords.requires_grad raises; there is no coordinate gradient), every level is at
@@ -48,95 +45,42 @@ out_dtype the backward runs on grad_out.float().
 import torch
 
 from . import _lib
-from ._lib import no_grad_inputs, require_device
+from ._grad import GradState, HandleFn, LookupFn
+from ._lib import check_coords
 
 
-class _AltGradState:
-    """What the backward of one trainable block shares: the geometry, the block's feature buffer, the
-    gradient feature buffer (allocated by the first lookup backward, freed by the pack backward) and
-    the consumed flag.  It references neither the block nor the handle: no cycle in the autograd graph."""
+class _AltGradState(GradState):
+    """The shared state of one trainable block (_grad.py): buf is the gradient feature buffer, laid out
+    as the block's feature buffer feat, which the state keeps (the backward reads it; no fmap is saved)."""
+
+    CONSUMED = ("eraft_amd AlternateCorrBlock: backward through a block whose gradient was already "
+                "consumed (one backward per trainable block)")
 
     def __init__(self, shape, levels, radius, feat, device):
-        self.shape, self.levels, self.radius, self.feat, self.device = shape, levels, radius, feat, device
-        self.grad_feat = None
-        self.consumed = False
+        super().__init__(shape, levels, radius, device, feat.numel())
+        self.feat = feat
 
-    def require_unconsumed(self):
-        if self.consumed:
-            raise RuntimeError("eraft_amd AlternateCorrBlock: backward through a block whose gradient was already "
-                               "consumed (one backward per trainable block)")
+    def lookup(self, feat, coords, out_dtype):
+        return _alt_lookup(feat, coords, self.shape, self.levels, self.radius, out_dtype)
 
-    def add_lookup_grad(self, grad, coords):
-        """grad_feat += the lookup's contribution: grad (contiguous fp32 [B, C, H, W]) at contiguous
-        coords, on grad's current stream.  The caller holds the device (on_device)."""
+    def lookup_backward(self, grad, coords):
         B, D, H, W = self.shape
         what = "AlternateCorrBlock lookup backward"
-        if self.grad_feat is None:
-            self.grad_feat = torch.zeros(self.feat.numel(), dtype=torch.float32, device=self.device)
         ws = _lib.scratch("ecorr_alt_backward_workspace_size", B, H, W, self.levels, self.radius, device=self.device,
                           what=what)
         _lib.check(_lib.lib().ecorr_alt_lookup_backward(
             self.feat.data_ptr(), coords.data_ptr(), grad.data_ptr(), B, D, H, W, self.levels, self.radius,
-            self.grad_feat.data_ptr(), ws.data_ptr(), _lib.stream_of(grad)), what)
+            self.buf.data_ptr(), ws.data_ptr(), _lib.stream_of(grad)), what)
 
-
-class _PackFn(torch.autograd.Function):
-    """(fmap1, fmap2) -> one-element handle; the features themselves are a buffer of the block."""
-
-    @staticmethod
-    def forward(ctx, fmap1, fmap2, state):
-        ctx.state = state
-        ctx.dtype = fmap1.dtype
-        return torch.zeros(1, dtype=torch.float32, device=state.device)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, _grad_handle):
-        st = ctx.state
-        st.require_unconsumed()
-        st.consumed = True
-        B, D, H, W = st.shape
-        n1, n2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gf, st.grad_feat = st.grad_feat, None
-        with _lib.on_device(st.device):
-            if gf is None:   # no lookup received a gradient
-                z = [torch.zeros(st.shape, dtype=ctx.dtype, device=st.device) if n else None for n in (n1, n2)]
-                return z[0], z[1], None
-            g1 = torch.empty(st.shape, dtype=torch.float32, device=st.device) if n1 else None
-            g2 = torch.empty(st.shape, dtype=torch.float32, device=st.device) if n2 else None
-            _lib.check(_lib.lib().ecorr_alt_pack_backward(
-                gf.data_ptr(), B, D, H, W, st.levels, _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(gf)),
-                "AlternateCorrBlock pack backward")
-            if ctx.dtype != torch.float32:   # 16-bit fmaps: the fp32 result cast once
-                g1 = None if g1 is None else g1.to(ctx.dtype)
-                g2 = None if g2 is None else g2.to(ctx.dtype)
-        return g1, g2, None
-
-
-class _AltLookupFn(torch.autograd.Function):
-    """(handle, coords) -> the lookup; backward adds into the block's gradient feature buffer."""
-
-    @staticmethod
-    def forward(ctx, handle, coords, state, out_dtype):
-        ctx.state = state
-        ctx.save_for_backward(coords)   # versioned: an in-place change before backward raises
-        return _alt_lookup(state.feat, coords.contiguous(), state.shape, state.levels, state.radius, out_dtype)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        st = ctx.state
-        st.require_unconsumed()
-        (coords,) = ctx.saved_tensors
-        go = grad_out.float().contiguous()   # a 16-bit lookup's gradient: the fp32 backward on its exact values
-        cc = coords.contiguous()
-        with _lib.on_device(st.device):
-            st.add_lookup_grad(go, cc)
-            return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None
+    def fmap_backward(self, gf, saved, g1, g2):
+        B, D, H, W = self.shape
+        _lib.check(_lib.lib().ecorr_alt_pack_backward(
+            gf.data_ptr(), B, D, H, W, self.levels, _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(gf)),
+            "AlternateCorrBlock pack backward")
 
 
 def _alt_lookup(feat, coords, shape, levels, radius, out_dtype):
-    """The ecorr_alt_lookup_as launch of the plain call and of _AltLookupFn.forward: contiguous, checked coords."""
+    """The ecorr_alt_lookup_as launch of the plain call and of the live block's LookupFn: contiguous, checked coords."""
     B, D, H, W = shape
     with _lib.on_device(feat.device):
         out = torch.empty((B, _lib.corr_channels(levels, radius), H, W), dtype=out_dtype, device=feat.device)
@@ -183,7 +127,7 @@ class AlternateCorrBlock:
         self._grad = self._handle = None
         if live:
             self._grad = _AltGradState(self._shape, num_levels, radius, self._feat, self._device)
-            self._handle = _PackFn.apply(fmap1, fmap2, self._grad)
+            self._handle = HandleFn.apply(fmap1, fmap2, self._grad)
 
     @property
     def corr_pyramid(self):
@@ -198,17 +142,7 @@ class AlternateCorrBlock:
         """The lookup [B, num_levels * (2r+1)^2, H, W]; out_dtype as CorrBlock.__call__'s."""
         out_dtype = _lib.lookup_out_dtype(out_dtype)
         B, D, H, W = self._shape
-        require_device("coords", coords)
+        check_coords(coords, (B, 2, H, W), self._device, self._grad is not None, "trainable AlternateCorrBlock")
         if self._grad is not None:
-            if torch.is_grad_enabled() and coords.requires_grad:
-                raise RuntimeError("trainable AlternateCorrBlock: coords requires grad; detach it (as eraft.py:127 "
-                                   "does), there is no gradient with respect to the coordinates")
-        else:
-            no_grad_inputs(coords)
-        if tuple(coords.shape) != (B, 2, H, W):
-            raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
-        if coords.device != self._device:
-            raise RuntimeError("coords is on a different device than the pyramid")
-        if self._grad is not None:
-            return _AltLookupFn.apply(self._handle, coords, self._grad, out_dtype)
+            return LookupFn.apply(self._handle, coords, self._grad, self._feat, out_dtype)
         return _alt_lookup(self._feat, coords.contiguous(), self._shape, self.num_levels, self.radius, out_dtype)

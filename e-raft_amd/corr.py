@@ -45,12 +45,10 @@ Training (opt-in): CorrBlock(fmap1, fmap2, num_levels, radius, differentiable=Tr
 that require grad and gives them gradients through the build and every `corr_fn(coords)` lookup
 (the two backward entries of csrc/grad.hip).  The forward runs
 the same launches, so its values are bitwise the plain block's; under torch.no_grad(), or when no
-fmap requires grad, the block is the plain block.  Autograd never carries a pyramid-sized tensor:
-the build is a Function of the fmaps returning a one-element handle, each lookup a Function of
-(handle, coords) whose backward adds its contribution into the block's single gradient pyramid
-(allocated and zeroed on the first one) and returns a zero for the handle; the build's backward
-then runs once, after all of them, turns the gradient pyramid into the two fmap gradients and
-frees it.  Deterministic (no atomics).  Contract of the differentiable block: coords are detached
+fmap requires grad, the block is the plain block.  Autograd never carries a pyramid-sized tensor
+(the handle mechanism of _grad.py: the lookups' backwards add into the block's single gradient
+pyramid, the build's backward runs once after all of them).  Deterministic (no atomics).
+Contract of the differentiable block: coords are detached
 (coords.requires_grad raises; eraft.py:127 detaches them; there is no coordinate gradient), every
 pyramid level is at least 2 x 2 (the reference's samples of a 1-pixel axis are NaN), D >= 1, one
 backward per block (a second one raises), single GPU; bilinear_sampler and RowShardedCorrBlock stay
@@ -83,99 +81,38 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import no_grad_inputs, require_device
+from ._grad import GradState, HandleFn, LookupFn
+from ._lib import check_coords, require_device
 from .layout import levels_of
 
 
-class _GradState:
-    """What the backward of one differentiable block shares: the geometry, the gradient pyramid G
-    (allocated by the first lookup backward, freed by the build backward) and the consumed flag.
-    It references neither the block nor the handle, so the autograd graph holds no cycle."""
+class _GradState(GradState):
+    """The shared state of one differentiable block (_grad.py): buf is the gradient pyramid G."""
 
-    def __init__(self, shape, levels, radius, numel, device):
-        self.shape, self.levels, self.radius, self.numel, self.device = shape, levels, radius, numel, device
-        self.G = None
-        self.consumed = False
+    CONSUMED = ("eraft_amd CorrBlock: backward through a block whose gradient was already "
+                "consumed (one backward per differentiable block)")
 
-    def require_unconsumed(self):
-        if self.consumed:
-            raise RuntimeError("eraft_amd CorrBlock: backward through a block whose gradient was already "
-                               "consumed (one backward per differentiable block)")
-
-    def add_lookup_grad(self, grad, coords):
-        """The one place a lookup's gradient enters G: grad (contiguous fp32 [B, C, H, W]) at contiguous
-        coords, on grad's current stream; G is allocated and zeroed by the first call.  The caller
-        holds the device (on_device) and returns the handle's gradient, a zero, itself: the two
-        lookup Functions make it at different points of their launch sequences."""
+    def lookup(self, pyramid, coords, out_dtype):
         B, _, H, W = self.shape
-        if self.G is None:
-            self.G = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        out = torch.empty((B, _lib.corr_channels(self.levels, self.radius), H, W), dtype=out_dtype,
+                          device=self.device)
+        return _lib.lookup(pyramid, coords, (B, H, W), H * W, self.levels, self.radius, out, "CorrBlock")
+
+    def lookup_backward(self, grad, coords):
+        B, _, H, W = self.shape
         _lib.check(_lib.lib().ecorr_lookup_backward(
-            grad.data_ptr(), coords.data_ptr(), B, H, W, H * W, self.levels, self.radius, self.G.data_ptr(),
+            grad.data_ptr(), coords.data_ptr(), B, H, W, H * W, self.levels, self.radius, self.buf.data_ptr(),
             _lib.stream_of(grad)), "CorrBlock lookup backward")
 
+    def saved(self, fmap1, fmap2):
+        return fmap1, fmap2   # as given: 16-bit fmaps (fmap_dtype) are saved as 16-bit
 
-class _BuildFn(torch.autograd.Function):
-    """(fmap1, fmap2) -> one-element handle; the pyramid itself is a buffer of the block."""
-
-    @staticmethod
-    def forward(ctx, fmap1, fmap2, state):
-        ctx.state = state
-        ctx.save_for_backward(fmap1, fmap2)   # as given: 16-bit fmaps (fmap_dtype) are saved as 16-bit
-        return torch.zeros(1, dtype=torch.float32, device=state.device)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, _grad_handle):
-        st = ctx.state
-        st.require_unconsumed()
-        st.consumed = True
-        f1, f2 = ctx.saved_tensors
-        B, D, H, W = st.shape
-        n1, n2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        G, st.G = st.G, None
-        dt = f1.dtype
-        with _lib.on_device(st.device):
-            if G is None:   # no lookup received a gradient
-                return (torch.zeros_like(f1) if n1 else None, torch.zeros_like(f2) if n2 else None, None)
-            # the backward is fp32: 16-bit fmaps as fp32 temporaries (exact), the gradients cast to the
-            # fmaps' dtype as autograd's own .float() node would hand them back
-            g1 = torch.empty(f1.shape, dtype=torch.float32, device=st.device) if n1 else None
-            g2 = torch.empty(f2.shape, dtype=torch.float32, device=st.device) if n2 else None
-            f1, f2 = f1.float(), f2.float()
-            _lib.check(_lib.lib().ecorr_build_backward(
-                G.data_ptr(), f1.data_ptr(), f2.data_ptr(), B, D, H, W, H * W, st.levels,
-                _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(f1)), "CorrBlock build backward")
-            if dt != torch.float32:
-                g1 = None if g1 is None else g1.to(dt)
-                g2 = None if g2 is None else g2.to(dt)
-        return g1, g2, None
-
-
-class _LookupFn(torch.autograd.Function):
-    """(handle, coords) -> the lookup; backward adds into the block's gradient pyramid."""
-
-    @staticmethod
-    def forward(ctx, handle, coords, state, pyramid, out_dtype=torch.float32):
-        ctx.state = state
-        ctx.save_for_backward(coords)   # versioned: an in-place change before backward raises
-        B, _, H, W = state.shape
-        out = torch.empty((B, _lib.corr_channels(state.levels, state.radius), H, W), dtype=out_dtype,
-                          device=state.device)
-        return _lib.lookup(pyramid, coords.contiguous(), (B, H, W), H * W, state.levels, state.radius, out,
-                           "CorrBlock")
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        st = ctx.state
-        st.require_unconsumed()
-        (coords,) = ctx.saved_tensors
-        go = grad_out.float().contiguous()   # a 16-bit lookup's gradient: the fp32 backward on its exact values
-        cc = coords.contiguous()
-        with _lib.on_device(st.device):
-            st.add_lookup_grad(go, cc)
-            return torch.zeros(1, dtype=torch.float32, device=st.device), None, None, None, None
+    def fmap_backward(self, G, saved, g1, g2):
+        B, D, H, W = self.shape
+        f1, f2 = (f.float() for f in saved)   # 16-bit fmaps as fp32 temporaries (exact)
+        _lib.check(_lib.lib().ecorr_build_backward(
+            G.data_ptr(), f1.data_ptr(), f2.data_ptr(), B, D, H, W, H * W, self.levels,
+            _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(f1)), "CorrBlock build backward")
 
 
 class _LookupConvFn(torch.autograd.Function):
@@ -282,8 +219,8 @@ class CorrBlock:
         self._colscale = None
         self._grad = self._handle = None
         if live:
-            self._grad = _GradState(self._shape, num_levels, radius, self._off[-1], self._device)
-            self._handle = _BuildFn.apply(fmap1, fmap2, self._grad)
+            self._grad = _GradState(self._shape, num_levels, radius, self._device, self._off[-1])
+            self._handle = HandleFn.apply(fmap1, fmap2, self._grad)
 
     @property
     def corr_pyramid(self):
@@ -298,28 +235,13 @@ class CorrBlock:
         rounded once to nearest-even: bitwise self(coords).to(out_dtype)); anything else: TypeError."""
         out_dtype = _lib.lookup_out_dtype(out_dtype)
         B, _, H, W = self._shape
-        self._check_coords(coords, train=self._grad is not None)
+        check_coords(coords, (B, 2, H, W), self._device, self._grad is not None, "differentiable CorrBlock")
         if self._grad is not None:
-            return _LookupFn.apply(self._handle, coords, self._grad, self._pyramid, out_dtype)
+            return LookupFn.apply(self._handle, coords, self._grad, self._pyramid, out_dtype)
         coords = coords.contiguous()   # the reference accepts any strides (permute + reshape)
         out = torch.empty((B, _lib.corr_channels(self.num_levels, self.radius), H, W), dtype=out_dtype,
                           device=self._device)
         return _lib.lookup(self._pyramid, coords, (B, H, W), H * W, self.num_levels, self.radius, out, "CorrBlock")
-
-    def _check_coords(self, coords, train):
-        """The coords checks of __call__ and lookup_conv1x1_relu; train: the call goes through autograd
-        (then coords that require grad are refused before the shape is looked at)."""
-        B, _, H, W = self._shape
-        require_device("coords", coords)
-        if train and torch.is_grad_enabled() and coords.requires_grad:
-            raise RuntimeError("differentiable CorrBlock: coords requires grad; detach it (as eraft.py:127 does), "
-                               "there is no gradient with respect to the coordinates")
-        if not train:
-            no_grad_inputs(coords)
-        if tuple(coords.shape) != (B, 2, H, W):
-            raise RuntimeError(f"coords shape {tuple(coords.shape)} != {(B, 2, H, W)} of the pyramid")
-        if coords.device != self._device:
-            raise RuntimeError("coords is on a different device than the pyramid")
 
     def lookup_conv1x1_relu(self, coords, weight, bias=None, mode=None, out_dtype=None):
         """F.relu(conv1x1(self(coords), weight, bias)): the lookup followed by
@@ -354,7 +276,8 @@ class CorrBlock:
         train = self._differentiable and torch.is_grad_enabled() and (
             self._grad is not None or (isinstance(weight, torch.Tensor) and weight.requires_grad)
             or (isinstance(bias, torch.Tensor) and bias.requires_grad))
-        self._check_coords(coords, train)
+        B, _, H, W = self._shape
+        check_coords(coords, (B, 2, H, W), self._device, train, "differentiable CorrBlock")
         if train:
             require_device("weight", weight)
             return _LookupConvFn.apply(self._handle, coords, weight, bias, self, mode, out_dtype)

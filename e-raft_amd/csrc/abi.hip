@@ -107,6 +107,17 @@ ECORR_EXPORT int ecorr_pyramid_formats(int H, int W, int levels, int* ntx) {
 
 namespace {
 
+// The scale step of the build and of the volume-free lookup: corr.py:60 divides by
+// torch.sqrt(torch.tensor(dim).float()) (IEEE sqrtf).  When that is a power of two the division is an
+// exact scaling and is done as a multiply (*is_mul, *scale = 1 / s, returns shift: s = 2^shift); else *scale = s.
+int scale_step_of(int D, float* scale, int* is_mul) {
+    const float s = sqrtf((float)D);
+    int e = 0;
+    *is_mul = frexpf(s, &e) == 0.5f ? 1 : 0;
+    *scale = *is_mul ? 1.0f / s : s;
+    return *is_mul ? e - 1 : 0;   // s = 0.5 * 2^e
+}
+
 // fmap_format (split build): ECORR_ELEM_* of the elements fmap1 / fmap2 point at; hi: workspace is a
 // hi workspace (the flag block, then the split workspace)
 int build_common(const float* fmap1, const float* fmap2, int B, int D, int H, int W, int q_count, int levels,
@@ -127,14 +138,7 @@ int build_common(const float* fmap1, const float* fmap2, int B, int D, int H, in
     P.H = H;
     P.W = W;
     P.q_count = q_count;
-    // corr.py:60 divides by torch.sqrt(torch.tensor(dim).float()) (IEEE sqrtf).  When that is a
-    // power of two the division is an exact scaling and is done as a multiply.
-    const float s = sqrtf((float)D);
-    int e = 0;
-    const float mant = frexpf(s, &e);
-    P.scale_is_mul = (mant == 0.5f) ? 1 : 0;
-    P.scale = P.scale_is_mul ? 1.0f / s : s;
-    P.scale_shift = P.scale_is_mul ? e - 1 : 0;   // s = 0.5 * 2^e
+    P.scale_shift = scale_step_of(D, &P.scale, &P.scale_is_mul);
     if (workspace) {
         if (B > 65535 || ((uintptr_t)workspace & 255)) return ECORR_EINVAL;
         P.ws = static_cast<char*>(workspace) + (hi ? kHiFlagBytes : 0);
@@ -486,12 +490,24 @@ namespace {
 
 bool elem_format_ok(int f) { return f == ECORR_ELEM_F32 || f == ECORR_ELEM_F16 || f == ECORR_ELEM_BF16; }
 
-// the build's scale step (build_common): / sqrtf(D), a multiply where that is a power of two
-void alt_scale_of(int D, float* scale, int* is_mul) {
-    const float s = sqrtf((float)D);
-    int e = 0;
-    *is_mul = frexpf(s, &e) == 0.5f ? 1 : 0;
-    *scale = *is_mul ? 1.0f / s : s;
+// what AltParams and AltGradParams share: the features' level table, the geometry, the scale step
+template <class Params>
+void alt_fill(Params& P, const float* feat, const float* coords, const AltGeom& g, int B, int D, int H, int W,
+              int levels, int radius) {
+    P.f1 = feat;
+    for (int i = 0; i < levels; ++i) {
+        P.lvl[i] = feat + g.off[i];
+        P.lh[i] = g.h[i];
+        P.lw[i] = g.w[i];
+    }
+    P.coords = coords;
+    P.B = B;
+    P.Dp = g.Dp;
+    P.Q = H * W;
+    P.levels = levels;
+    P.radius = radius;
+    P.C = levels * (2 * radius + 1) * (2 * radius + 1);
+    scale_step_of(D, &P.scale, &P.scale_is_mul);
 }
 
 }  // namespace
@@ -522,21 +538,8 @@ ECORR_EXPORT int ecorr_alt_lookup_as(const float* feat, const float* coords, int
     const int st = alt_geometry(B, D, H, W, levels, &g);
     if (st != ECORR_OK) return st;
     AltParams P{};
-    P.f1 = feat;
-    for (int i = 0; i < levels; ++i) {
-        P.lvl[i] = feat + g.off[i];
-        P.lh[i] = g.h[i];
-        P.lw[i] = g.w[i];
-    }
-    P.coords = coords;
+    alt_fill(P, feat, coords, g, B, D, H, W, levels, radius);
     P.out = out;
-    P.B = B;
-    P.Dp = g.Dp;
-    P.Q = H * W;
-    P.levels = levels;
-    P.radius = radius;
-    P.C = levels * (2 * radius + 1) * (2 * radius + 1);
-    alt_scale_of(D, &P.scale, &P.scale_is_mul);
     return launch_alt_lookup(P, out_format, (hipStream_t)stream);
 }
 
@@ -559,26 +562,15 @@ ECORR_EXPORT int ecorr_alt_lookup_backward(const float* feat, const float* coord
     const int st = alt_geometry(B, D, H, W, levels, &g);
     if (st != ECORR_OK) return st;
     AltGradParams P{};
-    P.f1 = feat;
+    alt_fill(P, feat, coords, g, B, D, H, W, levels, radius);
     P.g1 = grad_feat;
     for (int i = 0; i < levels; ++i) {
-        P.lvl[i] = feat + g.off[i];
         P.glvl[i] = grad_feat + g.off[i];
-        P.lh[i] = g.h[i];
-        P.lw[i] = g.w[i];
         P.lt0[i + 1] = P.lt0[i] + g.h[i] * g.w[i];
     }
-    P.coords = coords;
     P.grad_out = grad_out;
-    P.B = B;
-    P.Dp = g.Dp;
-    P.Q = H * W;
-    P.levels = levels;
-    P.radius = radius;
-    P.C = levels * (2 * radius + 1) * (2 * radius + 1);
     P.org = static_cast<int2*>(workspace);
     P.win = reinterpret_cast<float*>(P.org + (int64_t)B * levels * P.Q);
-    alt_scale_of(D, &P.scale, &P.scale_is_mul);
     return launch_alt_lookup_backward(P, (hipStream_t)stream);
 }
 

@@ -1106,7 +1106,7 @@ __global__ __launch_bounds__(NT, 3) void build_kernel(BuildParams P) {
     }
 
     // ---- scaled accumulators -> LDS C tile [m][n] in two 64-query halves; C/D map:
-    //      col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) ----
+    //      col = lane&31, row = mfma_c_row(reg, lane>>5) ----
     float* Cs = smem;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -1120,7 +1120,7 @@ __global__ __launch_bounds__(NT, 3) void build_kernel(BuildParams P) {
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const int m = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * arow;
+                            const int m = i * 32 + mfma_c_row(r, arow);
                             const int n = wn * 64 + j * 32 + acol;
                             Cs[m * CS + n] = scaled(acc[i][j][r]);
                         }

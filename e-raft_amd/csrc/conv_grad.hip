@@ -15,7 +15,7 @@
 //                            TRANSPOSED weight (launch_conv1x1_split_linear): the mask is materialized
 //                            because the conv's K loop counts its loads (no load may be added to it);
 //   grad_weight_kernel       an NT GEMM (both operands contiguous along p) on v_mfma_f32_32x32x2_f32,
-//                            fragments as grad.hip's build_backward_kernel; split-K: a workgroup
+//                            the frame of grad.hip's build_backward_kernel (mfma_f32_frame.h); split-K: a workgroup
 //                            reduces one slab of at most 1024 queries of one batch item (256 .. 1024 by
 //                            the shape, conv_grad_layout), so no fp32 accumulator chains more than
 //                            1024 terms (a 5000-term chain is 8e-6 .. 1e-5 normwise from fp64, slabs
@@ -28,21 +28,20 @@
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "mfma_f32_frame.h"
 
 namespace ecorr {
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 constexpr int MNT = 256;     // threads of every kernel here but the bias reduce
 constexpr int BNT = 1024;    // bias reduce: 16 waves
 constexpr int MQ = 64;       // mask pass: queries per workgroup (lane = query)
 constexpr int MR = 32;       // mask pass: channels per workgroup = one qmax group
-constexpr int WO = 256;      // grad_weight: o rows per workgroup (4 waves x 64)
-constexpr int WC = 64;       // grad_weight: c columns per workgroup
-constexpr int WK = 32;       // grad_weight: reduction chunk
-constexpr int WLD = WK + 1;  // LDS row stride (floats)
+constexpr int WO = kFrameM;  // grad_weight: o rows per workgroup (4 waves x 64)
+constexpr int WC = kFrameN;  // grad_weight: c columns per workgroup
+constexpr int WK = kFrameK;  // grad_weight: reduction chunk
+constexpr int WLD = kFrameLd;   // LDS row stride (floats)
 constexpr int kSlabMax = 1024;   // most reduction terms of one fp32 accumulator
 constexpr int kSlabMin = 256;    // the slab cap is halved down to this while the grid stays small
 constexpr int kSlabGrid = 480;   // ... below this many workgroups (a constant, not a device query)
@@ -153,8 +152,7 @@ __global__ __launch_bounds__(BNT) void bias_reduce_kernel(const float* __restric
 }
 
 // grid (slab sl = b * nsl + s, 256-row o block, 64-column c block): part[sl][o][c] = the slab's
-// sum_p gm[b][o][p] in[b][c][p].  Fragments as build_backward_kernel: A lane (m, kh) = gm[o = m][p = 2 s + kh],
-// B lane (n, kh) = in[c = n][p = 2 s + kh], C register r of lane (n, kh) = row (r & 3) + 8 (r >> 2) + 4 kh.
+// sum_p gm[b][o][p] in[b][c][p], on the frame of mfma_f32_frame.h: A = gm (row o, k = p), B = in (column c, k = p).
 // Rows past O, columns past C and queries past the slab's end are staged as zeros.
 __global__ __launch_bounds__(MNT) void grad_weight_kernel(const float* __restrict__ gm, const float* __restrict__ in,
                                                           int O, int C, int Q, int nsl, int slab,
@@ -170,12 +168,7 @@ __global__ __launch_bounds__(MNT) void grad_weight_kernel(const float* __restric
     const int nchunks = (p1 - p0 + WK - 1) / WK;
 
     floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    ECORR_FRAME_CLEAR(acc)
 
     float ro[WO / 8], rt[WC / 8];
     auto load_chunk = [&](int kc) {
@@ -199,30 +192,9 @@ __global__ __launch_bounds__(MNT) void grad_weight_kernel(const float* __restric
         for (int i = 0; i < WC / 8; ++i) tl[(dr + 8 * i) * WLD + kl] = rt[i];
     };
 
-    load_chunk(0);
-    for (int kc = 0; kc < nchunks; ++kc) {
-        __syncthreads();   // the previous chunk's fragment reads are done
-        store_chunk();
-        __syncthreads();
-        if (kc + 1 < nchunks) load_chunk(kc + 1);
-        const int m = lane & 31, kh = lane >> 5;
-#pragma unroll 4
-        for (int s = 0; s < WK / 2; ++s) {
-            const int k = 2 * s + kh;
-            float a[2], bf[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = ol[(64 * wave + 32 * i + m) * WLD + k];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = tl[(32 * j + m) * WLD + k];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-    }
+    ECORR_FRAME_K_LOOP(false, nchunks, ol, tl, lane, wave, acc, load_chunk, store_chunk)
 
-    // epilogue: lane (n, kh) holds column c, rows (r & 3) + 8 (r >> 2) + 4 kh of each 32 x 32 tile
+    // epilogue: lane (n, kh) holds column c, rows mfma_c_row(r, kh) of each 32 x 32 tile
     float* __restrict__ P = part + (int64_t)sl * O * C;
     const int kh = lane >> 5;
 #pragma unroll
@@ -233,7 +205,7 @@ __global__ __launch_bounds__(MNT) void grad_weight_kernel(const float* __restric
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int o = o0 + 64 * wave + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int o = mfma_c_row(r, kh, o0 + 64 * wave + 32 * i);
                 if (o < O) P[(int64_t)o * C + c] = acc[i][j][r];
             }
     }

@@ -106,7 +106,7 @@ __device__ __forceinline__ float unnormalize(float x, float size_m1, float half_
     return __fmul_rn(__fadd_rn(g, 1.0f), half_size_m1);
 }
 
-// The build's scale step on a finished sum (abi.hip build_common): / sqrtf(D), as a multiply where
+// The build's scale step on a finished sum (abi.hip scale_step_of): / sqrtf(D), as a multiply where
 // sqrtf(D) is a power of two (scale is then 1 / sqrtf(D)).  The volume-free lookup and its backward.
 __device__ __forceinline__ float scale_step(int is_mul, float scale, float s) {
     return is_mul ? __fmul_rn(s, scale) : __fdiv_rn(s, scale);

@@ -210,7 +210,7 @@ struct AltParams {
     const float* coords;               // [B][2][Q]
     void* out;                         // [B][C][Q] elements of the launch's out_format
     int B, Dp, Q, levels, radius, C;
-    float scale;                       // the build's scale step (abi.hip build_common)
+    float scale;                       // the scale step (abi.hip scale_step_of)
     int scale_is_mul;
 };
 int launch_alt_pack(const void* f1, const void* f2, int fmap_format, int B, int D, int H, int W, const AltGeom& g,
@@ -236,7 +236,7 @@ struct AltGradParams {
     int2* org;                            // workspace: [B][levels][Q] origins
     float* win;                           //            [B][levels][Q][(2r+3)^2] windows
     int B, Dp, Q, levels, radius, C;
-    float scale;                          // the build's scale step (abi.hip build_common)
+    float scale;                          // the scale step (abi.hip scale_step_of)
     int scale_is_mul;
 };
 int launch_alt_lookup_backward(const AltGradParams& P, hipStream_t stream);

@@ -17,6 +17,7 @@
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
 #include "lookup_grad_window.h"
+#include "mfma_f32_frame.h"
 
 namespace ecorr {
 
@@ -139,24 +140,18 @@ __global__ __launch_bounds__(NT) void fold_kernel(LookupGradParams P, int64_t ro
 //     padding cells carry zeros), op = fmap2[b][d][pixel of c], T(n, k) = T[b q + n][c]
 //   F2 = true  (grad_fmap2): n = stored cell c (outputs of padding cells are dropped), k = query p,
 //     op = fmap1[b][d][p], T(n, k) = T[b q + k][n]
-// Workgroup = 64 n x all of D (256 at a time: 4 waves of 64 d x 64 n = 2 x 2 MFMA tiles); the
-// reduction runs in chunks of 32 staged through LDS, the next chunk's global loads in flight under
-// the current chunk's MFMAs.  A chunk of T is whole 128-byte lines either way: 32 consecutive cells
-// of one row (one 4 x 8 tile).  Fragments as build_f32_kernel: A lane (m, kh) = op[m][2 s + kh],
-// B lane (n, kh) = T(n, 2 s + kh), C register r of lane (n, kh) = row (r & 3) + 8 (r >> 2) + 4 kh.
+// Workgroup = 64 n x all of D, 256 d at a time, on the frame of mfma_f32_frame.h (tile, staging, K loop
+// and fragments: A = op, B = T; shared with conv_grad.hip's grad_weight_kernel); the addressing and the
+// epilogue are this kernel's.  A chunk of T is whole 128-byte lines either way: 32 consecutive cells of
+// one row (one 4 x 8 tile).
 // ---------------------------------------------------------------------------------------------
-// (a local typedef, not split_f16.h's: tools/grad_emul.py rewrites this line to compile the file on
-// the CPU, where the ext_vector_type MFMA accumulator has no equivalent)
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int GD = 256;   // d rows per pass
-constexpr int GN = 64;    // output pixels per workgroup
-constexpr int GK = 32;    // reduction chunk
-constexpr int OLD = GK + 1;   // op tile row stride (floats)
+constexpr int GD = kFrameM;   // d rows per pass
+constexpr int GN = kFrameN;   // output pixels per workgroup
+constexpr int GK = kFrameK;   // reduction chunk
 
 template <bool F2>
 __global__ __launch_bounds__(NT) void build_backward_kernel(BuildGradParams P) {
-    constexpr int TLD = F2 ? GN + 1 : GK + 1;   // T tile: F2 [k][n], else [n][k]
+    constexpr int OLD = kFrameLd, TLD = kFrameBLd<F2>;   // T tile: F2 [k][n], else [n][k]
     __shared__ float ol[GD * OLD];
     __shared__ float tl[(F2 ? GK : GN) * TLD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -188,12 +183,7 @@ __global__ __launch_bounds__(NT) void build_backward_kernel(BuildGradParams P) {
 
     for (int d0 = 0; d0 < D; d0 += GD) {
         floatx16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+        ECORR_FRAME_CLEAR(acc)
 
         float ro[GD / 8], rt[8];
         auto load_chunk = [&](int kc) {
@@ -236,30 +226,9 @@ __global__ __launch_bounds__(NT) void build_backward_kernel(BuildGradParams P) {
             }
         };
 
-        load_chunk(0);
-        for (int kc = 0; kc < nchunks; ++kc) {
-            __syncthreads();   // the previous chunk's fragment reads are done
-            store_chunk();
-            __syncthreads();
-            if (kc + 1 < nchunks) load_chunk(kc + 1);
-            const int m = lane & 31, kh = lane >> 5;
-#pragma unroll 4
-            for (int s = 0; s < GK / 2; ++s) {
-                const int k = 2 * s + kh;
-                float a[2], bf[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) a[i] = ol[(64 * wave + 32 * i + m) * OLD + k];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) bf[j] = F2 ? tl[k * TLD + 32 * j + m] : tl[(32 * j + m) * TLD + k];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bf[j], acc[i][j], 0, 0, 0);
-            }
-        }
+        ECORR_FRAME_K_LOOP(F2, nchunks, ol, tl, lane, wave, acc, load_chunk, store_chunk)
 
-        // epilogue: lane (n, kh) holds column n, rows (r & 3) + 8 (r >> 2) + 4 kh of each 32 x 32 tile
+        // epilogue: lane (n, kh) holds column n, rows mfma_c_row(r, kh) of each 32 x 32 tile
         const int kh = lane >> 5;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -276,7 +245,7 @@ __global__ __launch_bounds__(NT) void build_backward_kernel(BuildGradParams P) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int d = d0 + 64 * wave + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                    const int d = mfma_c_row(r, kh, d0 + 64 * wave + 32 * i);
                     if (d < D) out[(int64_t)d * outld + col] = acc[i][j][r] / rs;
                 }
         }

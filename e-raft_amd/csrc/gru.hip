@@ -39,6 +39,7 @@
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "mfma_f32_frame.h"
 
 namespace ecorr {
 
@@ -208,14 +209,14 @@ __global__ __launch_bounds__(GNT, 2) void gru_gemm_kernel(const float* __restric
     compute(GNK - 1);   // the last chunk: nothing left to fetch, no barrier
     flush();
 
-    // ---- epilogue: lane holds pixel p, rows 32 rb + 8 (r >> 2) + 4 kh + (r & 3)
+    // ---- epilogue: lane holds pixel p, rows 32 rb + mfma_c_row(r, kh)
     if (!pok) return;
     const int64_t ib = (int64_t)b * GH * HW + p;   // (b, channel 0, p) of every [B][128][H W] tensor
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = 32 * (4 * rg + i) + 8 * (r >> 2) + 4 * kh + (r & 3);
+            const int o = 32 * (4 * rg + i) + mfma_c_row(r, kh);
             const float v = tot[i][r] + bias[o];
             if constexpr (QK) {
                 const float q = tanhf(v);

@@ -183,12 +183,12 @@ __global__ __launch_bounds__(NTM, 2) void lookup_conv_kernel(LookupParams P, con
 #pragma unroll
             for (int i = 0; i < 4; ++i) wc[i] = wn[i];
         }
-        // ---- epilogue: D map col = lane&31 (query), row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+        // ---- epilogue: D map col = lane&31 (query), row = mfma_c_row(reg, lane>>5)
         const int q = q0 + col;
         if (q < P.q_count && ob < O) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int orow = (r & 3) + 8 * (r >> 2) + 4 * kr;
+                const int orow = mfma_c_row(r, kr);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const int o = ob + 32 * i + orow;

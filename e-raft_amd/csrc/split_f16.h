@@ -7,9 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "mfma_f32_frame.h"   // floatx16
+
 namespace ecorr {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));

@@ -24,7 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from ._lib import no_grad_inputs, require_device
+from ._lib import check_coords, no_grad_inputs, require_device
 from .layout import levels_of
 
 
@@ -186,12 +186,7 @@ class RowShardedCorrBlock:
     def _local_coords(self, coords_rows):
         B, _, H, W = self._shape
         rr = self.counts[self.rank]
-        require_device("coords", coords_rows)
-        no_grad_inputs(coords_rows)
-        if tuple(coords_rows.shape) != (B, 2, rr, W):
-            raise RuntimeError(f"coords rows {tuple(coords_rows.shape)} != {(B, 2, rr, W)}")
-        if coords_rows.device != self._device:
-            raise RuntimeError("coords is on a different device than the pyramid")
+        check_coords(coords_rows, (B, 2, rr, W), self._device, rows=True)
         return coords_rows.contiguous()
 
     def _lookup_into(self, coords_rows, out):

@@ -346,7 +346,7 @@ def test_contract():
     zb = eraft_amd.AlternateCorrBlock(z1, z2, num_levels=3, radius=1, trainable=True)
     zb(coords)
     zb._handle.sum().backward()
-    assert zb._grad.consumed and zb._grad.grad_feat is None
+    assert zb._grad.consumed and zb._grad.buf is None
     assert int(torch.count_nonzero(z1.grad)) == 0 and int(torch.count_nonzero(z2.grad)) == 0
     # what stays refused
     with pytest.raises(RuntimeError, match="forward-only"):

@@ -319,5 +319,5 @@ def test_python_api_backward_branches():
     other = (f1 * f2).sum()
     (other + blk._handle.sum()).backward()
     torch.cuda.synchronize()
-    assert blk._grad.consumed and blk._grad.G is None   # _BuildFn.backward ran and no gradient pyramid ever existed
+    assert blk._grad.consumed and blk._grad.buf is None   # _BuildFn.backward ran and no gradient pyramid ever existed
     assert torch.equal(f1.grad, f2.detach()) and torch.equal(f2.grad, f1.detach())   # other's gradient plus exact zeros

@@ -128,7 +128,7 @@ def test_frozen_fmaps_train_weight_only(ea):
     assert g1 is None and g2 is None and blk._grad is None and blk._handle is None
     _, _, _, lw, lb, live = _ours(ea, case, "split", 256, live=True)
     assert torch.equal(gw, lw) and torch.equal(gb, lb)
-    assert live._grad.G is None   # the build backward freed the block's one gradient pyramid
+    assert live._grad.buf is None   # the build backward freed the block's one gradient pyramid
     # live block, frozen weight: fmap gradients only
     _, f1g, f2g, nw_, nb_, _ = _ours(ea, case, "split", 256, live=True, train_w=False)
     assert nw_ is None and nb_ is None and f1g is not None and f2g is not None

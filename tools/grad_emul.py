@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""csrc/grad.hip on the CPU: the kernel source itself (two textual substitutions: the dynamic LDS
-declaration and the MFMA accumulator type) compiled as C++ against tools/grad_emul/shim (one host
-thread per GPU thread) with AddressSanitizer + UBSan, run as a stand-alone program on a case of
+"""csrc/grad.hip on the CPU: the kernel source itself (one textual substitution: the dynamic LDS
+declaration) and the headers it includes, csrc/mfma_f32_frame.h among them, compiled as C++ against
+tools/grad_emul/shim (one host thread per GPU thread; it maps the MFMA accumulator's ext_vector_type
+onto g++'s vector_size) with AddressSanitizer + UBSan, run as a stand-alone program on a case of
 tests/backward_cases.py and compared with the reference's gradients (tests/golden/backward_*.npz).
 For finding an out-of-bounds access or a wrong index without a GPU; it says nothing about speed.
     python tools/grad_emul.py d3_l3r1 [y0 y1]      # optional query-row slab
@@ -36,9 +37,7 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         src = open(os.path.join(CSRC, "grad.hip")).read()
         src, n1 = re.subn(r"extern __shared__ float lds\[\];", "float* lds = g_dynlds;", src)
-        src, n2 = re.subn(r"typedef float floatx16 __attribute__\(\(ext_vector_type\(16\)\)\);",
-                          "typedef emul_f16 floatx16;", src)
-        assert n1 == 1 and n2 == 1
+        assert n1 == 1
         open(os.path.join(d, "grad_emul.cpp"), "w").write(src)
         exe = os.path.join(d, "emul")
         subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-ffp-contract=off",

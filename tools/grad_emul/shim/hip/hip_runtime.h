@@ -37,6 +37,9 @@ inline float __fadd_rn(float a, float b) { return a + b; }
 inline float __fsub_rn(float a, float b) { return a - b; }
 inline float __fmul_rn(float a, float b) { return a * b; }
 inline float __fdiv_rn(float a, float b) { return a / b; }
+// csrc/mfma_f32_frame.h: `typedef float floatx16 __attribute__((ext_vector_type(16)))` is clang's; g++ has
+// the same 16 subscriptable floats as vector_size (bytes)
+#define ext_vector_type(n) vector_size(sizeof(float) * (n))
 typedef float emul_f16 __attribute__((vector_size(64)));
 inline emul_f16 emul_mfma(float a, float b, emul_f16 acc) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
