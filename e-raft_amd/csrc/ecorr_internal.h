@@ -279,7 +279,7 @@ int launch_voxel(bool dsec, const float* p, const float* t, const float* x, cons
                  int64_t n, int C, int H, int W, int normalize, float* voxel, int* bad, void* workspace,
                  hipStream_t stream);
 
-int64_t splat_workspace_bytes(bool flow_mode, int B, int64_t n, int h, int w);
+int64_t splat_workspace_bytes(int B, int64_t n, int h, int w);
 int launch_splat(bool flow_mode, const float* pts, int B, int64_t n, int h, int w, float* values, uint8_t* valid,
                  void* workspace, hipStream_t stream);
 

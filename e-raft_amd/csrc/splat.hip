@@ -9,34 +9,34 @@
 // contributions serially in (pass, point) order.  A float atomicAdd scatter would sum them in
 // arrival order, so instead the scatter is inverted into a gather with a counting sort:
 //   1. count contributions per target        (LDS atomics, integer: order-free)
-//   2. exclusive scan of the counts          (block scan)
+//   2. exclusive scan of the counts          (block scan, sort_fold.h)
 //   3. drop each contribution's key (pass, s) into its target's bucket; integer atomics pick the
 //      slot, in rounds of consecutive keys, so a bucket is sorted up to the keys of one round
 //   4. per target: insertion-sort the (nearly sorted) bucket, then fold the contributions
 //      recomputed from the keys in ascending key order = the reference's order, bit for bit.
-// One 1024-thread workgroup per batch item; E-RAFT's flows are 1/8-resolution maps (<= 14720
-// points at 1280x720), so the counts live in LDS (<= 16384 targets) and the work is latency-bound
-// (a few microseconds), not bandwidth-bound: in LDS mode (DSEC, MVSEC) all four phases run out of
-// LDS; larger maps keep keys (and counts past 16384 targets) in the caller's workspace.
+// E-RAFT's flows are 1/8-resolution maps (<= 14720 points at 1280x720): the work is latency-bound (a
+// few microseconds), not bandwidth-bound.  Maps up to kBandMaxN points take the banded kernel below,
+// all in LDS; larger ones splat_kernel, one 1024-thread workgroup per batch item with its keys (and
+// its counts past kLdsTargets targets) in the caller's workspace.
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "sort_fold.h"
 
 namespace ecorr {
 
 namespace {
 
 constexpr int NTS = 1024;
-constexpr int kLdsTargets = 16384;   // global mode: counts in LDS up to this many targets
-constexpr int kPool = 36864;         // LDS mode: 144 KB holds counts, keys and the points
+constexpr int kLdsTargets = 16384;   // counts in LDS up to this many targets
 constexpr int kPassShift = 24;       // key = pass << 24 | point (n < 2^24, checked at the ABI)
 
 struct SplatArgs {
     const float* pts;   // FLOW: flow [B][2][n] (n = h*w); else points [3][n] (x, y, z)
     float* values;      // [B][nz][h*w]
     uint8_t* valid;     // [B][h*w] or null
-    int* ws_count;      // [B][h*w] (global mode with h*w > kLdsTargets)
-    int* ws_keys;       // [B][4n] (global mode)
+    int* ws_count;      // splat_kernel: [B][h*w] (h*w > kLdsTargets)
+    int* ws_keys;       // splat_kernel: [B][4n]
     int64_t n;
     int h, w;
 };
@@ -45,7 +45,7 @@ struct SplatArgs {
 template <bool FLOW> constexpr int kPtFloats = FLOW ? 2 : 3;
 
 // The point s: position and value channels, from `src` = the item's point data ([k][n] planes,
-// global or its LDS copy).
+// global or an LDS copy).
 template <bool FLOW>
 __device__ __forceinline__ void point(const float* src, int n, int w, float rcp_w, int s, float& x, float& y, float* z) {
     if (FLOW) {
@@ -78,33 +78,63 @@ __device__ __forceinline__ int target_of(int pass, float x, float y, int h, int 
     return (int)__fadd_rn(xv, __fmul_rn((float)w, yv));
 }
 
-// LDS mode (counts + keys + points fit kPool: every E-RAFT size up to DSEC, and MVSEC): the item's
-// points are staged into LDS once and all four phases run out of LDS.  Global mode: counts in LDS
-// when they fit, keys in the workspace, points re-read from global memory.
-template <bool FLOW, bool LDS>
+// One target's sums, values and weight, folded from +0 (put_ into torch.zeros).
+template <bool FLOW>
+struct TargetSum {
+    static constexpr int NZ = FLOW ? 2 : 1;
+    float acc[NZ], wacc = 0.0f;
+    __device__ __forceinline__ TargetSum() {
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) acc[c] = 0.0f;
+    }
+    // one contribution: term[c] = z[c] * wgt
+    __device__ __forceinline__ void add(const float* term, float wgt) {
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) acc[c] = __fadd_rn(acc[c], term[c]);
+        wacc = __fadd_rn(wacc, wgt);
+    }
+    // image_utils.py:44 values_ipl / (weights_acc + 1e-15) -> target t of item b, and its `valid`
+    __device__ __forceinline__ void store(const SplatArgs& A, int b, int t) const {
+        const int64_t hw = (int64_t)A.h * A.w;
+        const float den = __fadd_rn(wacc, 1e-15f);
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) A.values[(b * NZ + c) * hw + t] = __fdiv_rn(acc[c], den);
+        if (A.valid) A.valid[b * hw + t] = wacc > 0.0f;
+    }
+};
+
+// The fold of the contributions keys[lo, hi), each recomputed from its key; ascending keys = the
+// reference's serial (pass, point) order, bit for bit.
+template <bool FLOW>
+__device__ __forceinline__ TargetSum<FLOW> fold_keys(const SplatArgs& A, const float* src, float rcp_w, const int* keys,
+                                                     int lo, int hi) {
+    constexpr int NZ = TargetSum<FLOW>::NZ;
+    TargetSum<FLOW> sum;
+    for (int i = lo; i < hi; ++i) {
+        const int e = keys[i];
+        float x, y, z[NZ], wgt = 0.0f;
+        point<FLOW>(src, (int)A.n, A.w, rcp_w, e & ((1 << kPassShift) - 1), x, y, z);
+        target_of(e >> kPassShift, x, y, A.h, A.w, wgt);
+#pragma unroll
+        for (int c = 0; c < NZ; ++c) z[c] = __fmul_rn(z[c], wgt);
+        sum.add(z, wgt);
+    }
+    return sum;
+}
+
+// Maps past kBandMaxN points: one workgroup per item, counts in LDS when they fit, keys in the
+// workspace, points re-read from global memory.
+template <bool FLOW>
 __global__ __launch_bounds__(NTS) void splat_kernel(SplatArgs A) {
     constexpr int NZ = FLOW ? 2 : 1, NP = kPtFloats<FLOW>;
-    __shared__ int pool[LDS ? kPool : kLdsTargets];
+    __shared__ int pool[kLdsTargets];
     __shared__ int wsum[NTS / kWave];
-    __shared__ int carry_s;
     const int tid = threadIdx.x, b = blockIdx.x;
     const int n = (int)A.n, hw = A.h * A.w, ne = 4 * n;
-    const float* gpts = A.pts + (int64_t)b * NP * n;
+    const float* src = A.pts + (int64_t)b * NP * n;
     const float rcp_w = 1.0f / (float)A.w;
-    int* cnt;
-    int* keys;
-    const float* src;
-    if (LDS) {
-        cnt = pool;
-        keys = pool + hw;
-        float* lp = reinterpret_cast<float*>(pool + hw + ne);
-        for (int i = tid; i < NP * n; i += NTS) lp[i] = gpts[i];
-        src = lp;
-    } else {
-        cnt = hw <= kLdsTargets ? pool : A.ws_count + (int64_t)b * hw;
-        keys = A.ws_keys + (int64_t)b * ne;
-        src = gpts;
-    }
+    int* cnt = hw <= kLdsTargets ? pool : A.ws_count + (int64_t)b * hw;
+    int* keys = A.ws_keys + (int64_t)b * ne;
 
     for (int t = tid; t < hw; t += NTS) cnt[t] = 0;
     __syncthreads();
@@ -121,36 +151,25 @@ __global__ __launch_bounds__(NTS) void splat_kernel(SplatArgs A) {
     }
     __syncthreads();
 
-    // 2. exclusive scan; each thread owns SPT consecutive counts of a super-chunk
+    // 2. exclusive scan; each thread owns SPT consecutive counts of a super-chunk, `carry` = the
+    // total of the super-chunks before it
     constexpr int SPT = 8;
-    if (tid == 0) carry_s = 0;
-    const int lane = tid & (kWave - 1), wv = tid / kWave;
+    int carry = 0;
     for (int c0 = 0; c0 < hw; c0 += NTS * SPT) {
-        __syncthreads();
         const int t0 = c0 + tid * SPT;
-        int v[SPT], sum = 0;
+        int v[SPT], sum = 0, total;
 #pragma unroll
         for (int j = 0; j < SPT; ++j) {
             v[j] = t0 + j < hw ? cnt[t0 + j] : 0;
             sum += v[j];
         }
-        int inc = sum;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int u = __shfl_up(inc, d, kWave);
-            if (lane >= d) inc += u;
-        }
-        if (lane == kWave - 1) wsum[wv] = inc;
-        __syncthreads();
-        int run = carry_s + inc - sum;
-        for (int i = 0; i < wv; ++i) run += wsum[i];
+        int run = carry + block_exclusive_scan<NTS>(sum, wsum, total);
 #pragma unroll
         for (int j = 0; j < SPT; ++j) {
             if (t0 + j < hw) cnt[t0 + j] = run;
             run += v[j];
         }
-        __syncthreads();
-        if (tid == NTS - 1) carry_s = run;
+        carry += total;
     }
     __syncthreads();
 
@@ -171,7 +190,6 @@ __global__ __launch_bounds__(NTS) void splat_kernel(SplatArgs A) {
         }
 
     // 4. per target: order the bucket, fold in key order from +0 (put_ into torch.zeros)
-    float* vout = A.values + (int64_t)b * NZ * hw;
     for (int t = tid; t < hw; t += NTS) {
         const int lo = t > 0 ? cnt[t - 1] : 0, hi = cnt[t];
         for (int i = lo + 1; i < hi; ++i) {
@@ -180,24 +198,7 @@ __global__ __launch_bounds__(NTS) void splat_kernel(SplatArgs A) {
             while (j >= lo && keys[j] > k) { keys[j + 1] = keys[j]; --j; }
             keys[j + 1] = k;
         }
-        float acc[NZ], wacc = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) acc[c] = 0.0f;
-        for (int i = lo; i < hi; ++i) {
-            const int e = keys[i];
-            const int pass = e >> kPassShift;
-            float x, y, z[NZ], wgt = 0.0f;
-            point<FLOW>(src, n, A.w, rcp_w, e & ((1 << kPassShift) - 1), x, y, z);
-            target_of(pass, x, y, A.h, A.w, wgt);
-#pragma unroll
-            for (int c = 0; c < NZ; ++c) acc[c] = __fadd_rn(acc[c], __fmul_rn(z[c], wgt));
-            wacc = __fadd_rn(wacc, wgt);
-        }
-        // :44 values_ipl / (weights_acc + 1e-15)
-        const float den = __fadd_rn(wacc, 1e-15f);
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) vout[c * hw + t] = __fdiv_rn(acc[c], den);
-        if (A.valid) A.valid[(int64_t)b * hw + t] = wacc > 0.0f;
+        fold_keys<FLOW>(A, src, rcp_w, keys, lo, hi).store(A, b, t);
     }
 }
 
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(NTB) void splat_band_kernel(SplatArgs A, int G) {
     __shared__ int cnt[kBandTargets + 1];
     __shared__ int lkey[kBandCap], ltgt[kBandCap], keys[kBandCap], stgt[kBandCap];
     __shared__ int wsum[NTB / kWave];
-    __shared__ int nlist, carry_s;
+    __shared__ int nlist, nsub_s;
     __shared__ int sub[kBandTargets + 1];   // sub-range boundaries (overflow path)
     // one linear block index (band fastest): no gridDim.y limit on the batch (B > 65535 launches)
     const int tid = threadIdx.x, band = (int)(blockIdx.x % (unsigned)G), b = (int)(blockIdx.x / (unsigned)G);
@@ -317,57 +318,28 @@ __global__ __launch_bounds__(NTB) void splat_band_kernel(SplatArgs A, int G) {
 
     // 2. exclusive scan of cnt[0 .. nb) (nb <= kBandTargets <= NTB * 2): two per thread
     {
-        const int lane = tid & (kWave - 1), wv = tid / kWave;
         const int i0 = 2 * tid;
         const int v0 = i0 < nb ? cnt[i0] : 0, v1 = i0 + 1 < nb ? cnt[i0 + 1] : 0;
-        const int sum = v0 + v1;
-        int inc = sum;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int u = __shfl_up(inc, d, kWave);
-            if (lane >= d) inc += u;
-        }
-        if (lane == kWave - 1) wsum[wv] = inc;
-        __syncthreads();
-        int run = inc - sum;
-        for (int i = 0; i < wv; ++i) run += wsum[i];
-        __syncthreads();
+        int total;
+        const int run = block_exclusive_scan<NTB>(v0 + v1, wsum, total);
         if (i0 < nb) cnt[i0] = run;
         if (i0 + 1 < nb) cnt[i0 + 1] = run + v0;
-        if (tid == NTB - 1) cnt[nb] = run + sum;   // total
+        if (tid == 0) cnt[nb] = total;
     }
     __syncthreads();
     // cnt[t] = start of target t's bucket, cnt[nb] = the band's total
 
-    float* vout = A.values + (int64_t)b * NZ * hw;
     // 4. per target: fold its bucket, already in key order (sorted[lo, hi)), or (huge) fold target t
     // by walking every contribution in key order
     auto fold_sorted = [&](const int* sorted, int t, int lo, int hi) {
-        float acc[NZ], wacc = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) acc[c] = 0.0f;
-        for (int i = lo; i < hi; ++i) {
-            const int e = sorted[i];
-            float x, y, z[NZ], wgt = 0.0f;
-            point<FLOW>(src, n, A.w, rcp_w, e & ((1 << kPassShift) - 1), x, y, z);
-            target_of(e >> kPassShift, x, y, A.h, A.w, wgt);
-#pragma unroll
-            for (int c = 0; c < NZ; ++c) acc[c] = __fadd_rn(acc[c], __fmul_rn(z[c], wgt));
-            wacc = __fadd_rn(wacc, wgt);
-        }
-        const float den = __fadd_rn(wacc, 1e-15f);   // :44 values_ipl / (weights_acc + 1e-15)
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) vout[c * hw + t0 + t] = __fdiv_rn(acc[c], den);
-        if (A.valid) A.valid[(int64_t)b * hw + t0 + t] = wacc > 0.0f;
+        fold_keys<FLOW>(A, src, rcp_w, sorted, lo, hi).store(A, b, t0 + t);
     };
     // one wave (one thread walking 4n contributions took 3.4 ms at DSEC): its lanes
     // evaluate 64 consecutive contributions of a pass at once, then the hits are folded one after
     // another in lane (= point) order from the lanes' products -- the serial fold, bit for bit
     auto fold_walk = [&](int t) {
         const int lane = __lane_id();
-        float acc[NZ], wacc = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) acc[c] = 0.0f;
+        TargetSum<FLOW> sum;
         for (int pass = 0; pass < 4; ++pass)
             for (int s0 = 0; s0 < n; s0 += kWave) {
                 const int s = s0 + lane;
@@ -382,23 +354,19 @@ __global__ __launch_bounds__(NTB) void splat_band_kernel(SplatArgs A, int G) {
                 }
                 for (uint64_t m = __builtin_amdgcn_ballot_w64(hit); m; m &= m - 1) {
                     const int l = (int)__builtin_ctzll(m);
+                    float from_l[NZ];
 #pragma unroll
-                    for (int c = 0; c < NZ; ++c) acc[c] = __fadd_rn(acc[c], __shfl(term[c], l, kWave));
-                    wacc = __fadd_rn(wacc, __shfl(wgt, l, kWave));
+                    for (int c = 0; c < NZ; ++c) from_l[c] = __shfl(term[c], l, kWave);
+                    sum.add(from_l, __shfl(wgt, l, kWave));
                 }
             }
-        if (lane != 0) return;
-        const float den = __fadd_rn(wacc, 1e-15f);
-#pragma unroll
-        for (int c = 0; c < NZ; ++c) vout[c * hw + t0 + t] = __fdiv_rn(acc[c], den);
-        if (A.valid) A.valid[(int64_t)b * hw + t0 + t] = wacc > 0.0f;
+        if (lane == 0) sum.store(A, b, t0 + t);
     };
 
     const int total = cnt[nb];
     if (total <= kBandCap) {   // block-uniform: the common case
         // 3. bucket the listed keys (cnt[t] walks to the next bucket's start), then order each
-        // bucket by rank: slot i's key goes to lo + #{keys of its bucket smaller than it} (keys are
-        // distinct) -- k independent LDS reads per slot, so a heavy bucket costs depth k, not k^2
+        // bucket by rank (sort_fold.h)
         for (int i = tid; i < total; i += NTB) {
             const int t = ltgt[i];
             const int slot = atomicAdd(&cnt[t], 1);
@@ -409,9 +377,7 @@ __global__ __launch_bounds__(NTB) void splat_band_kernel(SplatArgs A, int G) {
         for (int i = tid; i < total; i += NTB) {
             const int t = stgt[i], k = keys[i];
             const int lo = t > 0 ? cnt[t - 1] : 0, hi = cnt[t];
-            int r = 0;
-            for (int j = lo; j < hi; ++j) r += keys[j] < k;
-            lkey[lo + r] = k;
+            lkey[lo + rank_in_run(lo, hi, k, [&](int j) { return keys[j]; })] = k;
         }
         __syncthreads();
         for (int t = tid; t < nb; t += NTB) fold_sorted(lkey, t, t > 0 ? cnt[t - 1] : 0, cnt[t]);
@@ -428,10 +394,10 @@ __global__ __launch_bounds__(NTB) void splat_band_kernel(SplatArgs A, int G) {
             sub[++r] = e;
             a = e;
         }
-        carry_s = r;
+        nsub_s = r;
     }
     __syncthreads();
-    const int nsub = carry_s;
+    const int nsub = nsub_s;
     for (int r = 0; r < nsub; ++r) {
         const int a = sub[r], e = sub[r + 1];
         const int base = cnt[a];
@@ -462,18 +428,12 @@ __global__ __launch_bounds__(NTB) void splat_band_kernel(SplatArgs A, int G) {
         for (int i = tid; i < cnt[e] - base; i += NTB) {
             const int t = ltgt[i], k = keys[i];
             const int lo = cnt[t] - base, hi = cnt[t + 1] - base;
-            int rk = 0;
-            for (int j = lo; j < hi; ++j) rk += keys[j] < k;
-            stgt[lo + rk] = k;
+            stgt[lo + rank_in_run(lo, hi, k, [&](int j) { return keys[j]; })] = k;
         }
         __syncthreads();
         for (int t = a + tid; t < e; t += NTB) fold_sorted(stgt, t, cnt[t] - base, cnt[t + 1] - base);
         __syncthreads();
     }
-}
-
-bool lds_mode(bool flow_mode, int64_t n, int64_t hw) {
-    return hw + 4 * n + (flow_mode ? 2 : 3) * n <= kPool;
 }
 
 bool band_mode(int64_t n) { return n <= kBandMaxN; }
@@ -489,9 +449,9 @@ int band_count(int B, int64_t hw) {
 
 }  // namespace
 
-int64_t splat_workspace_bytes(bool flow_mode, int B, int64_t n, int h, int w) {
+int64_t splat_workspace_bytes(int B, int64_t n, int h, int w) {
     const int64_t hw = (int64_t)h * w;
-    if (band_mode(n) || lds_mode(flow_mode, n, hw)) return 0;
+    if (band_mode(n)) return 0;
     return (int64_t)B * ((hw > kLdsTargets ? hw : 0) + 4 * n) * (int64_t)sizeof(int);
 }
 
@@ -516,11 +476,8 @@ int launch_splat(bool flow_mode, const float* pts, int B, int64_t n, int h, int 
         else hipLaunchKernelGGL((splat_band_kernel<false>), grid, dim3(NTB), 0, stream, A, G);
         return hip_status();
     }
-    const bool lds = lds_mode(flow_mode, n, hw);
-    if (flow_mode && lds) hipLaunchKernelGGL((splat_kernel<true, true>), dim3(B), dim3(NTS), 0, stream, A);
-    else if (flow_mode) hipLaunchKernelGGL((splat_kernel<true, false>), dim3(B), dim3(NTS), 0, stream, A);
-    else if (lds) hipLaunchKernelGGL((splat_kernel<false, true>), dim3(B), dim3(NTS), 0, stream, A);
-    else hipLaunchKernelGGL((splat_kernel<false, false>), dim3(B), dim3(NTS), 0, stream, A);
+    if (flow_mode) hipLaunchKernelGGL((splat_kernel<true>), dim3(B), dim3(NTS), 0, stream, A);
+    else hipLaunchKernelGGL((splat_kernel<false>), dim3(B), dim3(NTS), 0, stream, A);
     return hip_status();
 }
 

@@ -13,8 +13,8 @@
 //   bucket  counting sort by key: per event its arrival rank in its key (one returning integer
 //           atomic, in prep), exclusive scan of the counts (reduce -> scan of the tile sums ->
 //           tile scans, 16-byte loads and stores), each event and its weight factors (one float4)
-//           dropped at run start + rank -- no second atomic pass (round 6: the two random-atomic
-//           passes were 96 of the 282 us per DSEC window, profiles/r06_lab);
+//           dropped at run start + rank -- no second atomic pass (random global atomics are the
+//           pipeline's most expensive step);
 //   order   per key with two or more events, its run insertion-sorted by event index (runs are
 //           short and the atomics hand out ranks nearly in event order, so this is ~linear) and
 //           the run's weight factors re-gathered into that order;
@@ -31,6 +31,7 @@
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "sort_fold.h"
 
 namespace ecorr {
 
@@ -46,6 +47,35 @@ __device__ __forceinline__ int x86_i32(float v) {
 }
 __device__ __forceinline__ long long x86_i64(double v) {
     return (v >= -9223372036854775808.0 && v < 9223372036854775808.0) ? (long long)v : (long long)(1ULL << 63);
+}
+
+// dsec_utils.py:35-41 for event e of a window starting at t0 and lasting dt (Args: VoxelArgs or
+// VTileArgs): t_norm, value, the truncated base cell (x0, y0, ti) and whether any of its 8 corner
+// passes lands on the grid -- corners x0 .. x0 + 1 touch [0, W) iff x0 in [-1, W - 1].
+struct DsecEvent {
+    float tn, val;
+    int x0, y0, ti;
+    bool in;
+};
+template <class Args>
+__device__ __forceinline__ DsecEvent dsec_event(const Args& A, int64_t e, float t0, float dt) {
+    DsecEvent v;
+    // :35 (C - 1) * (t - t[0]) / (t[-1] - t[0])
+    v.tn = __fdiv_rn(__fmul_rn((float)(A.C - 1), __fsub_rn(A.t[e], t0)), dt);
+    v.val = __fsub_rn(__fmul_rn(2.0f, A.p[e]), 1.0f);   // :41 value = 2*p - 1
+    v.x0 = x86_i32(A.x[e]);
+    v.y0 = x86_i32(A.y[e]);
+    v.ti = x86_i32(v.tn);
+    v.in = v.x0 >= -1 && v.x0 < A.W && v.y0 >= -1 && v.y0 < A.H && v.ti >= -1 && v.ti < A.C;
+    return v;
+}
+
+// :48 value * (1 - |xlim - x|) * (1 - |ylim - y|) * (1 - |tlim - t_norm|), left to right; ev = the
+// event's (x, y, t_norm, value)
+__device__ __forceinline__ float vt_term(float4 ev, float fx, float fy, float ft) {
+    float wgt = __fmul_rn(ev.w, __fsub_rn(1.0f, fabsf(__fsub_rn(fx, ev.x))));
+    wgt = __fmul_rn(wgt, __fsub_rn(1.0f, fabsf(__fsub_rn(fy, ev.y))));
+    return __fmul_rn(wgt, __fsub_rn(1.0f, fabsf(__fsub_rn(ft, ev.z))));
 }
 
 struct VoxelArgs {
@@ -71,18 +101,15 @@ struct VoxelArgs {
 __global__ __launch_bounds__(NTV) void prep_dsec(VoxelArgs A) {
     const int64_t e = blockIdx.x * (int64_t)NTV + threadIdx.x;
     if (e >= A.n) return;
-    const float t0 = A.t[0], dt = __fsub_rn(A.t[A.n - 1], t0);
-    // dsec_utils.py:35 (C - 1) * (t - t[0]) / (t[-1] - t[0])
-    const float tn = __fdiv_rn(__fmul_rn((float)(A.C - 1), __fsub_rn(A.t[e], t0)), dt);
-    const int x0 = x86_i32(A.x[e]), y0 = x86_i32(A.y[e]), ti = x86_i32(tn);
-    // base cell on the grid extended by one on the low side: corners x0 .. x0+1 touch [0, W) iff
-    // x0 in [-1, W-1]
-    const bool in = x0 >= -1 && x0 < A.W && y0 >= -1 && y0 < A.H && ti >= -1 && ti < A.C;
-    const uint32_t k = in ? (uint32_t)(((int64_t)(ti + 1) * (A.H + 1) + (y0 + 1)) * (A.W + 1) + (x0 + 1)) : A.K;
+    const float t0 = A.t[0];
+    const DsecEvent v = dsec_event(A, e, t0, __fsub_rn(A.t[A.n - 1], t0));
+    // base cell on the grid extended by one on the low side
+    const uint32_t k =
+        v.in ? (uint32_t)(((int64_t)(v.ti + 1) * (A.H + 1) + (v.y0 + 1)) * (A.W + 1) + (v.x0 + 1)) : A.K;
     A.key[e] = k;
-    if (in) A.rank[e] = atomicAdd(&A.cnt[k], 1u);
-    A.fa[e] = tn;
-    A.fb[e] = __fsub_rn(__fmul_rn(2.0f, A.p[e]), 1.0f);   // :41 value = 2*p - 1
+    if (v.in) A.rank[e] = atomicAdd(&A.cnt[k], 1u);
+    A.fa[e] = v.tn;
+    A.fb[e] = v.val;
 }
 
 __global__ __launch_bounds__(NTV) void prep_mvsec(VoxelArgs A) {
@@ -182,6 +209,33 @@ __device__ __forceinline__ Moments block_moments(Moments m, double* sh) {
     return {sh[0], sh[1], sh[2]};
 }
 
+// A thread's nonzero cells as plain fp64 sums (no division per cell), turned into (count, mean, M2)
+// once, before the block's fixed-order Chan tree.
+struct CellSums {
+    double n = 0.0, s = 0.0, ss = 0.0;
+    __device__ __forceinline__ void add(float acc) {
+        if (acc == 0.0f) return;
+        const double v = (double)acc;
+        n += 1.0;
+        s += v;
+        ss = fma(v, v, ss);
+    }
+    __device__ __forceinline__ Moments moments() const {
+        if (!(n > 0.0)) return {0.0, 0.0, 0.0};
+        const double mean = s / n;
+        return {n, mean, fmax(ss - s * mean, 0.0)};
+    }
+    // the block's tree (sh: 3 * NTV doubles of LDS, free to overwrite) and its partial -> part[0 .. 3)
+    __device__ __forceinline__ void store_block(double* sh, double* part) const {
+        const Moments m = block_moments(moments(), sh);
+        if (threadIdx.x == 0) {
+            part[0] = m.n;
+            part[1] = m.mean;
+            part[2] = m.m2;
+        }
+    }
+};
+
 // Block = a contiguous range of grid rows (tc, yc); its threads walk the range's cells in order,
 // 256 apart, with (row, xc) stepped incrementally (no per-cell integer division; every lane busy
 // whatever W is); the keys of a cell's 8 passes are the row's base key + xc minus constants
@@ -192,9 +246,7 @@ __global__ __launch_bounds__(NTV) void gather(VoxelArgs A, int normalize) {
     const int rows = A.C * A.H;
     const int per = (rows + gridDim.x - 1) / gridDim.x;
     const int r0 = blockIdx.x * per, r1 = min(rows, r0 + per);
-    // this thread's nonzero cells as plain fp64 sums (no division per cell), turned into (count,
-    // mean, M2) once before the block's fixed-order Chan tree
-    double cn = 0.0, cs = 0.0, css = 0.0;
+    CellSums sums;
     const uint32_t dB = (uint32_t)A.W + 1, dC = ((uint32_t)A.H + 1) * dB;
     int r = r0 + (int)threadIdx.x / A.W, xc = (int)threadIdx.x % A.W;
     int tc = r / A.H, yc = r - tc * A.H;
@@ -218,14 +270,8 @@ __global__ __launch_bounds__(NTV) void gather(VoxelArgs A, int normalize) {
 #pragma unroll
                 for (int pass = 0; pass < 8; ++pass) {
                     const int aa = pass >> 2, bc = pass & 3;
-                    for (uint32_t j = o3[bc][1 - aa]; j < o3[bc][2 - aa]; ++j) {
-                        const float4 ev = A.payload[j];
-                        // :48 value * (1 - |xlim - x|) * (1 - |ylim - y|) * (1 - |tlim - t_norm|), left to right
-                        float wgt = __fmul_rn(ev.w, __fsub_rn(1.0f, fabsf(__fsub_rn(fx, ev.x))));
-                        wgt = __fmul_rn(wgt, __fsub_rn(1.0f, fabsf(__fsub_rn(fy, ev.y))));
-                        wgt = __fmul_rn(wgt, __fsub_rn(1.0f, fabsf(__fsub_rn(ft, ev.z))));
-                        acc = __fadd_rn(acc, wgt);
-                    }
+                    for (uint32_t j = o3[bc][1 - aa]; j < o3[bc][2 - aa]; ++j)
+                        acc = __fadd_rn(acc, vt_term(A.payload[j], fx, fy, ft));
                 }
             } else {
                 // transformers.py:103-113: all left contributions, then all right ones (+W*H)
@@ -236,12 +282,7 @@ __global__ __launch_bounds__(NTV) void gather(VoxelArgs A, int normalize) {
                 for (uint32_t j = rr.x; j < rr.y; ++j) acc = __fadd_rn(acc, A.payload[j].y);
             }
             A.voxel[(int64_t)r * A.W + xc] = acc;
-            if (normalize && acc != 0.0f) {
-                const double v = (double)acc;
-                cn += 1.0;
-                cs += v;
-                css = fma(v, v, css);
-            }
+            if (normalize) sums.add(acc);
         }
         xc += NTV;   // next cell of this thread: 256 further in row-major order
         while (xc >= A.W) {
@@ -250,19 +291,7 @@ __global__ __launch_bounds__(NTV) void gather(VoxelArgs A, int normalize) {
             if (++yc == A.H) { yc = 0; ++tc; }
         }
     }
-    if (normalize) {   // uniform over the grid
-        Moments mom{0.0, 0.0, 0.0};
-        if (cn > 0.0) {
-            const double mean = cs / cn;
-            mom = {cn, mean, fmax(css - cs * mean, 0.0)};
-        }
-        const Moments m = block_moments(mom, sh);
-        if (threadIdx.x == 0) {
-            A.part[3 * blockIdx.x] = m.n;
-            A.part[3 * blockIdx.x + 1] = m.mean;
-            A.part[3 * blockIdx.x + 2] = m.m2;
-        }
-    }
+    if (normalize) sums.store_block(sh, A.part + 3 * blockIdx.x);   // uniform over the grid
 }
 
 // ---- normalization (dsec_utils.py:55-62, transformers.py:117-124)
@@ -348,28 +377,6 @@ void launch_norm_apply(float* g, int64_t n, const NormState* st, hipStream_t str
 // phase 3 scans each tile from its offset.  Integer arithmetic: exact in any order.
 constexpr int SCAN_PER = 16, SCAN_T = NTV * SCAN_PER;
 
-static_assert(NTV % 64 == 0 && NTV <= 1024, "block_exclusive_scan: whole 64-lane waves, sh[NTV / 64]");
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) sh[wv] = x;
-    __syncthreads();
-    uint32_t pre = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < NTV / 64; ++w) {
-        if (w < wv) pre += sh[w];
-        sum += sh[w];
-    }
-    total = sum;
-    __syncthreads();
-    return pre + x - v;
-}
-
 // A thread's SCAN_PER consecutive counts: four 16-byte loads (the arrays are 256-byte aligned), the
 // range's tail element by element.
 __device__ __forceinline__ void load16(const uint32_t* __restrict__ in, int64_t base, int64_t K, uint32_t (&v)[SCAN_PER]) {
@@ -386,25 +393,25 @@ __device__ __forceinline__ void load16(const uint32_t* __restrict__ in, int64_t 
 }
 
 __global__ __launch_bounds__(NTV) void scan_reduce(const uint32_t* __restrict__ in, int64_t K, uint32_t* __restrict__ sums) {
-    __shared__ uint32_t sh[NTV / 64];
+    __shared__ uint32_t sh[NTV / kWave];
     const int64_t base = (int64_t)blockIdx.x * SCAN_T + threadIdx.x * SCAN_PER;
     uint32_t w[SCAN_PER], v = 0;
     load16(in, base, K, w);
 #pragma unroll
     for (int k = 0; k < SCAN_PER; ++k) v += w[k];
     uint32_t total;
-    block_exclusive_scan(v, sh, total);
+    block_exclusive_scan<NTV>(v, sh, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(NTV) void scan_sums(uint32_t* __restrict__ sums, int nb) {
-    __shared__ uint32_t sh[NTV / 64];
+    __shared__ uint32_t sh[NTV / kWave];
     uint32_t carry = 0;
     for (int c = 0; c < nb; c += NTV) {
         const int i = c + threadIdx.x;
         const uint32_t v = i < nb ? sums[i] : 0;
         uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, sh, total);
+        const uint32_t ex = block_exclusive_scan<NTV>(v, sh, total);
         if (i < nb) sums[i] = carry + ex;
         carry += total;
     }
@@ -412,14 +419,14 @@ __global__ __launch_bounds__(NTV) void scan_sums(uint32_t* __restrict__ sums, in
 
 __global__ __launch_bounds__(NTV) void scan_apply(const uint32_t* __restrict__ in, int64_t K, const uint32_t* __restrict__ sums,
                                                   uint32_t* __restrict__ out) {
-    __shared__ uint32_t sh[NTV / 64];
+    __shared__ uint32_t sh[NTV / kWave];
     const int64_t base = (int64_t)blockIdx.x * SCAN_T + threadIdx.x * SCAN_PER;
     uint32_t v[SCAN_PER], s = 0;
     load16(in, base, K, v);
 #pragma unroll
     for (int k = 0; k < SCAN_PER; ++k) s += v[k];
     uint32_t total;
-    uint32_t run = sums[blockIdx.x] + block_exclusive_scan(s, sh, total);
+    uint32_t run = sums[blockIdx.x] + block_exclusive_scan<NTV>(s, sh, total);
     uint32_t o[SCAN_PER];
 #pragma unroll
     for (int k = 0; k < SCAN_PER; ++k) {
@@ -504,17 +511,6 @@ __device__ __forceinline__ int vt_window(const VTileArgs& A, int ey, int ex, int
     return (ty >= 0 && ty < A.gy && tx >= 0 && tx < A.gx) ? ty * A.gx + tx : -1;
 }
 
-// dsec_utils.py:35-41 as prep_dsec: t_norm, value and the extended base cell of event e; false when
-// the event lies in no window (no pass of it lands on the grid)
-__device__ __forceinline__ bool vt_prep(const VTileArgs& A, int64_t e, float t0, float dt, float& tn, float& val,
-                                        int& ey, int& ex) {
-    tn = __fdiv_rn(__fmul_rn((float)(A.C - 1), __fsub_rn(A.t[e], t0)), dt);
-    val = __fsub_rn(__fmul_rn(2.0f, A.p[e]), 1.0f);
-    const int x0 = x86_i32(A.x[e]), y0 = x86_i32(A.y[e]), ti = x86_i32(tn);
-    ey = y0 + 1;
-    ex = x0 + 1;
-    return x0 >= -1 && x0 < A.W && y0 >= -1 && y0 < A.H && ti >= -1 && ti < A.C;
-}
 static_assert(VB_EPB <= 65536, "16-bit slots within (window, block)");
 
 __global__ __launch_bounds__(VB_CNT) void vb_count(VTileArgs A) {
@@ -527,13 +523,12 @@ __global__ __launch_bounds__(VB_CNT) void vb_count(VTileArgs A) {
     for (int k = 0; k < VB_EPB / VB_CNT; ++k) {
         const int64_t e = (int64_t)blk * VB_EPB + k * VB_CNT + tid;
         if (e >= A.n) break;
-        float tn, val;
-        int ey, ex;
-        if (vt_prep(A, e, t0, dt, tn, val, ey, ex)) {
+        const DsecEvent v = dsec_event(A, e, t0, dt);
+        if (v.in) {   // else the event lies in no window
             uint32_t sl[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int w = vt_window(A, ey, ex, q);
+                const int w = vt_window(A, v.y0 + 1, v.x0 + 1, q);
                 sl[q] = w >= 0 ? atomicAdd(&hist[w], 1u) : 0u;
             }
             A.slot[e] = make_uint2(sl[0] | sl[1] << 16, sl[2] | sl[3] << 16);
@@ -579,7 +574,7 @@ __global__ __launch_bounds__(NTV) void vb_starts(VTileArgs A) {
         for (int j = 0; j < 8; ++j) s += v[j];
     }
     uint32_t total;
-    uint32_t run = block_exclusive_scan(s, sh, total);
+    uint32_t run = block_exclusive_scan<NTV>(s, sh, total);
     for (int k = k0; k < k1; ++k) {
         A.S[k] = run;
         run += A.tot[k];
@@ -589,17 +584,16 @@ __global__ __launch_bounds__(NTV) void vb_starts(VTileArgs A) {
 __global__ __launch_bounds__(NTV) void vb_scatter(VTileArgs A) {
     const int64_t e = blockIdx.x * (int64_t)NTV + threadIdx.x;
     if (e >= A.n) return;
-    const float t0 = A.t[0], dt = __fsub_rn(A.t[A.n - 1], t0);
-    float tn, val;
-    int ey, ex;
-    if (!vt_prep(A, e, t0, dt, tn, val, ey, ex)) return;   // the same arithmetic as vb_count's
+    const float t0 = A.t[0];
+    const DsecEvent d = dsec_event(A, e, t0, __fsub_rn(A.t[A.n - 1], t0));
+    if (!d.in) return;
     const uint2 s = A.slot[e];
     const uint32_t sl[4] = {s.x & 0xffff, s.x >> 16, s.y & 0xffff, s.y >> 16};
-    const float4 v = make_float4(A.x[e], A.y[e], tn, val);
+    const float4 v = make_float4(A.x[e], A.y[e], d.tn, d.val);
     const uint32_t* Mrow = A.M + (e / VB_EPB) * A.nb;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const int w = vt_window(A, ey, ex, q);
+        const int w = vt_window(A, d.y0 + 1, d.x0 + 1, q);
         if (w < 0) continue;
         const uint32_t i = A.S[w] + Mrow[w] + sl[q];
         A.pay[i].ev = v;
@@ -616,13 +610,6 @@ struct VWin {
     int wsum[VB_NT / kWave];
 };
 static_assert(sizeof(float4) * VB_CAP >= 3 * sizeof(double) * VB_NT, "moments scratch");
-
-// :48 value * (1 - |xlim - x|) * (1 - |ylim - y|) * (1 - |tlim - t_norm|), left to right
-__device__ __forceinline__ float vt_term(float4 ev, float fx, float fy, float ft) {
-    float wgt = __fmul_rn(ev.w, __fsub_rn(1.0f, fabsf(__fsub_rn(fx, ev.x))));
-    wgt = __fmul_rn(wgt, __fsub_rn(1.0f, fabsf(__fsub_rn(fy, ev.y))));
-    return __fmul_rn(wgt, __fsub_rn(1.0f, fabsf(__fsub_rn(ft, ev.z))));
-}
 
 __global__ __launch_bounds__(VB_NT) void vb_gather(VTileArgs A, int normalize) {
     __shared__ VWin L;
@@ -651,25 +638,16 @@ __global__ __launch_bounds__(VB_NT) void vb_gather(VTileArgs A, int normalize) {
         atomicAdd(&L.off[run_of(ev)], 1);
     }
     __syncthreads();
-    {   // exclusive scan of the nrun counts: per thread a contiguous chunk, waves, then the block
+    {   // exclusive scan of the nrun counts: per thread a contiguous chunk
         constexpr int PER = (VB_MAXRUN + VB_NT - 1) / VB_NT;
         const int k0 = tid * PER;
-        int v[PER], s = 0;
+        int v[PER], s = 0, total;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             v[i] = k0 + i < nrun ? L.off[k0 + i] : 0;
             s += v[i];
         }
-        int inc = s;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int u = __shfl_up(inc, d, kWave);
-            if (lane >= d) inc += u;
-        }
-        if (lane == kWave - 1) L.wsum[wv] = inc;
-        __syncthreads();
-        int base = inc - s;
-        for (int w = 0; w < wv; ++w) base += L.wsum[w];
+        int base = block_exclusive_scan<VB_NT>(s, L.wsum, total);
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             if (k0 + i < nrun) L.off[k0 + i] = base;
@@ -687,16 +665,8 @@ __global__ __launch_bounds__(VB_NT) void vb_gather(VTileArgs A, int normalize) {
     for (int j = tid; j < n; j += VB_NT) {   // rank within the run by event index
         const int r = run_of(ar ? gc[j].ev : L.ev[j]);
         const int lo = r > 0 ? L.off[r - 1] : 0, hi = L.off[r];
-        int rk = 0;
-        if (ar) {
-            const int me = gc[j].idx;
-            for (int i = lo; i < hi; ++i) rk += gc[aord[i]].idx < me;
-            aords[lo + rk] = (uint32_t)j;
-        } else {
-            const int me = L.idx[j];
-            for (int i = lo; i < hi; ++i) rk += L.idx[L.ord[i]] < me;
-            L.ords[lo + rk] = (unsigned short)j;
-        }
+        if (ar) aords[lo + rank_in_run(lo, hi, gc[j].idx, [&](int i) { return gc[aord[i]].idx; })] = (uint32_t)j;
+        else L.ords[lo + rank_in_run(lo, hi, L.idx[j], [&](int i) { return L.idx[L.ord[i]]; })] = (unsigned short)j;
     }
     __syncthreads();
 
@@ -713,7 +683,7 @@ __global__ __launch_bounds__(VB_NT) void vb_gather(VTileArgs A, int normalize) {
     const int ly = lane / VB_TX, lx = lane % VB_TX;
     const int yc = ey0 + ly, xc = ex0 + lx;
     const int nper = (A.C + VB_NW - 1) / VB_NW, tc0 = wv * nper, tc1 = min(A.C, tc0 + nper);
-    double cn = 0.0, cs = 0.0, css = 0.0;
+    CellSums sums;
     if (yc < A.H && xc < A.W && tc0 < tc1) {
         const float fx = (float)xc, fy = (float)yc;
         // run bounds of bin e around this cell: row ly + 1 (u) and row ly (d), columns lx and lx + 1:
@@ -747,28 +717,13 @@ __global__ __launch_bounds__(VB_NT) void vb_gather(VTileArgs A, int normalize) {
                 acc = __fadd_rn(acc, vt_term(ar ? gc[aords[i]].ev : L.ev[i], fx, fy, ft));
             }
             A.voxel[((int64_t)tc * A.H + yc) * A.W + xc] = acc;
-            if (normalize && acc != 0.0f) {
-                const double v = (double)acc;
-                cn += 1.0;
-                cs += v;
-                css = fma(v, v, css);
-            }
+            if (normalize) sums.add(acc);
             bp = bn;
         }
     }
-    if (normalize) {   // (count, mean, M2) of this thread's nonzero cells, then a fixed-order tree
-        Moments m{0.0, 0.0, 0.0};
-        if (cn > 0.0) {
-            const double mean = cs / cn;
-            m = {cn, mean, fmax(css - cs * mean, 0.0)};
-        }
+    if (normalize) {
         __syncthreads();   // the fold's reads of L.ev are done: its bytes become the scratch
-        m = block_moments(m, reinterpret_cast<double*>(L.ev));
-        if (tid == 0) {
-            A.part[3 * tile] = m.n;
-            A.part[3 * tile + 1] = m.mean;
-            A.part[3 * tile + 2] = m.m2;
-        }
+        sums.store_block(reinterpret_cast<double*>(L.ev), A.part + 3 * tile);
     }
 }
 
@@ -787,7 +742,18 @@ inline bool vtile_geom(int64_t n, int C, int H, int W, VTileGeom* g) {
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// Workspace carve-up (every piece 256-byte aligned).
+// Workspace carve-up: take(bytes) = the offset of the next piece, every piece 256-byte aligned;
+// `at` = the bytes taken so far.
+struct Carve {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t o = at;
+        at += align256(bytes);
+        return o;
+    }
+};
+
+// Workspace of the key-range pipeline.
 struct VoxelWs {
     size_t key, rank, cnt, off, slot, fa, fb, payload, norm, part, scan_sums, total;
 };
@@ -796,23 +762,20 @@ struct VoxelWs {
 // blocks at DSEC) was slower, 88 vs 75 us, and its 18,000 partials cost the one-block finalize 31 us
 constexpr int kGatherBlocks = 2048;
 
-int plan(int64_t n, uint32_t K, int64_t cells, VoxelWs* w) {
-    (void)cells;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-    w->key = take(4 * (size_t)n);
-    w->rank = take(4 * (size_t)n);
-    w->cnt = take(4 * ((size_t)K + 1));
-    w->off = take(4 * ((size_t)K + 1));
-    w->slot = take(4 * (size_t)n);
-    w->fa = take(4 * (size_t)n);
-    w->fb = take(4 * (size_t)n);
-    w->payload = take(16 * (size_t)n);
-    w->norm = take(sizeof(NormState));
-    w->part = take(3 * 8 * (size_t)kGatherBlocks);
-    w->scan_sums = take(4 * (((size_t)K + 1 + SCAN_T - 1) / SCAN_T));
-    w->total = o;
-    return ECORR_OK;
+void plan(int64_t n, uint32_t K, VoxelWs* w) {
+    Carve c;
+    w->key = c.take(4 * (size_t)n);
+    w->rank = c.take(4 * (size_t)n);
+    w->cnt = c.take(4 * ((size_t)K + 1));
+    w->off = c.take(4 * ((size_t)K + 1));
+    w->slot = c.take(4 * (size_t)n);
+    w->fa = c.take(4 * (size_t)n);
+    w->fb = c.take(4 * (size_t)n);
+    w->payload = c.take(16 * (size_t)n);
+    w->norm = c.take(sizeof(NormState));
+    w->part = c.take(3 * 8 * (size_t)kGatherBlocks);
+    w->scan_sums = c.take(4 * (((size_t)K + 1 + SCAN_T - 1) / SCAN_T));
+    w->total = c.at;
 }
 
 // Workspace of the tiled DSEC path.
@@ -821,19 +784,18 @@ struct VTileWs {
 };
 
 void plan_tiled(int64_t n, const VTileGeom& g, VTileWs* w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+    Carve c;
     const size_t copies = 4 * (size_t)n;   // an event lies in at most 4 windows
-    w->slot = take(8 * (size_t)n);
-    w->M = take(4 * (size_t)g.nblk * g.nb);
-    w->tot = take(4 * ((size_t)g.nb + 1));
-    w->S = take(4 * ((size_t)g.nb + 1));
-    w->pay = take(sizeof(VCopy) * copies);
-    w->norm = take(sizeof(NormState));
-    w->part = take(3 * 8 * (size_t)g.nb);
-    w->aord = take(4 * copies);
-    w->aords = take(4 * copies);
-    w->total = o;
+    w->slot = c.take(8 * (size_t)n);
+    w->M = c.take(4 * (size_t)g.nblk * g.nb);
+    w->tot = c.take(4 * ((size_t)g.nb + 1));
+    w->S = c.take(4 * ((size_t)g.nb + 1));
+    w->pay = c.take(sizeof(VCopy) * copies);
+    w->norm = c.take(sizeof(NormState));
+    w->part = c.take(3 * 8 * (size_t)g.nb);
+    w->aord = c.take(4 * copies);
+    w->aords = c.take(4 * copies);
+    w->total = c.at;
 }
 
 int launch_voxel_tiled(const float* p, const float* t, const float* x, const float* y, int64_t n, int C, int H,
@@ -884,9 +846,9 @@ int voxel_workspace_bytes(bool dsec, int64_t n, int C, int H, int W, int64_t* by
         return ECORR_OK;
     }
     VoxelWs w;
-    const int st = plan(n, voxel_key_range(dsec, C, H, W), (int64_t)C * H * W, &w);
-    if (st == ECORR_OK) *bytes = (int64_t)w.total;
-    return st;
+    plan(n, voxel_key_range(dsec, C, H, W), &w);
+    *bytes = (int64_t)w.total;
+    return ECORR_OK;
 }
 
 int launch_voxel(bool dsec, const float* p, const float* t, const float* x, const float* y, const double* ev,
@@ -900,9 +862,8 @@ int launch_voxel(bool dsec, const float* p, const float* t, const float* x, cons
     A.n = n; A.C = C; A.H = H; A.W = W;
     A.K = voxel_key_range(dsec, C, H, W);
     VoxelWs w;
-    const int64_t cells = (int64_t)C * H * W;
-    int st = plan(n, A.K, cells, &w);
-    if (st != ECORR_OK) return st;
+    plan(n, A.K, &w);
+    int st;
     char* base = (char*)workspace;
     A.key = (uint32_t*)(base + w.key);
     A.rank = (uint32_t*)(base + w.rank);
@@ -942,7 +903,7 @@ int launch_voxel(bool dsec, const float* p, const float* t, const float* x, cons
     if ((st = hip_status()) != ECORR_OK) return st;
     if (normalize) {
         hipLaunchKernelGGL(norm_finalize, dim3(1), dim3(NTV), 0, stream, A.part, (int)gblocks, ns);
-        launch_norm_apply(voxel, cells, ns, stream);
+        launch_norm_apply(voxel, (int64_t)C * H * W, ns, stream);
     }
     return hip_status();
 }

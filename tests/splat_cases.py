@@ -3,7 +3,7 @@ infrastructure, numpy only.  Shared by tests/test_dispatch_mirrors.py (on the CP
 constants against the source, every branch covered) and tests/test_splat_dispatch_gpu.py.
 
 launch_splat takes the banded kernel (splat_band_kernel, G bands of targets per item, one workgroup
-each) for n <= kBandMaxN points per item, else splat_kernel<*, false>, one workgroup per item with its
+each) for n <= kBandMaxN points per item, else splat_kernel, one workgroup per item with its
 keys -- and, past kLdsTargets targets, its counts -- in the caller's workspace.  The banded kernel
 stages an item's points in LDS while they fit kBandPts floats (16-byte loads where the item's pointer
 is 16-byte aligned, else scalar ones), serves a band whose contributions fit kBandCap from its LDS
@@ -38,12 +38,12 @@ def kernel(n):
 
 
 def workspace_needed(n):
-    """splat_workspace_bytes > 0: the large-map kernel's keys (lds_mode never holds past kBandMaxN points)."""
+    """splat_workspace_bytes > 0: the large-map kernel's keys."""
     return kernel(n) == "large"
 
 
 def counts(hw):
-    """splat_kernel<*, false>: cnt = hw <= kLdsTargets ? pool : ws_count"""
+    """splat_kernel: cnt = hw <= kLdsTargets ? pool : ws_count"""
     return "lds" if hw <= kLdsTargets else "ws"
 
 

@@ -598,8 +598,8 @@ PATCHES["sp_stamps"] = [
      "    __syncthreads();\n    sps(1);\n    const float* src = staged ? spts : gpts;\n"),
     ("splat.hip", "    __syncthreads();\n\n    // 2. exclusive scan of cnt[0 .. nb)", "    __syncthreads();\n    sps(2);\n\n    // 2. exclusive scan of cnt[0 .. nb)"),
     ("splat.hip", "    __syncthreads();\n    // cnt[t] = start of target t's bucket", "    __syncthreads();\n    sps(3);\n    // cnt[t] = start of target t's bucket"),
-    ("splat.hip", "            lkey[lo + r] = k;\n        }\n        __syncthreads();\n",
-     "            lkey[lo + r] = k;\n        }\n        __syncthreads();\n        sps(4);\n"),
+    ("splat.hip", "[&](int j) { return keys[j]; })] = k;\n        }\n        __syncthreads();\n        for (int t = tid; t < nb;",
+     "[&](int j) { return keys[j]; })] = k;\n        }\n        __syncthreads();\n        sps(4);\n        for (int t = tid; t < nb;"),
     ("splat.hip", "        for (int t = tid; t < nb; t += NTB) fold_sorted(lkey, t, t > 0 ? cnt[t - 1] : 0, cnt[t]);\n        return;\n",
      "        for (int t = tid; t < nb; t += NTB) fold_sorted(lkey, t, t > 0 ? cnt[t - 1] : 0, cnt[t]);\n        __syncthreads();\n        sps(5);\n        return;\n"),
     ("splat.hip", "}  // namespace ecorr\n", "}  // namespace ecorr\n" + SPS_EXPORT),
