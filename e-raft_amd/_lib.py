@@ -127,6 +127,14 @@ SYMBOLS = {
     "ecorr_sepconv_gru_pack": (_i, [ctypes.POINTER(_p), ctypes.POINTER(_p), _i, _i, _p, _p]),
     "ecorr_sepconv_gru_workspace_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "ecorr_sepconv_gru": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    # its backward (added within ABI 17): (hidden, input, bytes*) / (weight[6], hidden, input, packed_t, stream) /
+    # (B, hidden, input, H, W, bytes*) / (h, x, grad_out, B, hidden, input, H, W, packed, packed_t, grad_h, grad_x,
+    # grad_weight[6], grad_bias[6], workspace, stream)
+    "ecorr_sepconv_gru_backward_packed_size": (_i, [_i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_sepconv_gru_backward_pack": (_i, [ctypes.POINTER(_p), _i, _i, _p, _p]),
+    "ecorr_sepconv_gru_backward_workspace_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_sepconv_gru_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, ctypes.POINTER(_p),
+                                        ctypes.POINTER(_p), _p, _p]),
     "ecorr_bilinear_sampler": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
     "ecorr_coords_grid": (_i, [_i, _i, _i, _p, _p]),
     # (chunks, chunk, world, B, C, H, W, out, stream)

@@ -623,6 +623,72 @@ ECORR_EXPORT int ecorr_sepconv_gru(const float* h, const float* x, int B, int hi
     return launch_gru(h, x, B, H, W, packed, h_out, workspace, (hipStream_t)stream);
 }
 
+ECORR_EXPORT int ecorr_sepconv_gru_backward_packed_size(int hidden, int input, int64_t* bytes) {
+    if (!bytes || !gru_sizes_ok(hidden, input)) return ECORR_EINVAL;
+    *bytes = gru_packed_t_bytes();
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_sepconv_gru_backward_pack(const float* const weight[6], int hidden, int input, void* packed_t,
+                                                 void* stream) {
+    if (!weight || !packed_t || ((uintptr_t)packed_t & 15) || !gru_sizes_ok(hidden, input)) return ECORR_EINVAL;
+    for (int i = 0; i < 6; ++i)
+        if (!weight[i]) return ECORR_EINVAL;
+    return launch_gru_pack_t(weight, packed_t, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_sepconv_gru_backward_workspace_size(int B, int hidden, int input, int H, int W,
+                                                           int64_t* bytes) {
+    if (!bytes || !gru_sizes_ok(hidden, input) || !gru_geometry_ok(B, H, W)) return ECORR_EINVAL;
+    *bytes = gru_backward_workspace_bytes(B, H, W);
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_sepconv_gru_backward(const float* h, const float* x, const float* grad_out, int B, int hidden,
+                                            int input, int H, int W, const void* packed, const void* packed_t,
+                                            float* grad_h, float* grad_x, float* const grad_weight[6],
+                                            float* const grad_bias[6], void* workspace, void* stream) {
+    if (!h || !x || !grad_out || !packed || !packed_t || !workspace || !gru_sizes_ok(hidden, input) ||
+        !gru_geometry_ok(B, H, W))
+        return ECORR_EINVAL;
+    if (((uintptr_t)packed & 15) || ((uintptr_t)packed_t & 15) || ((uintptr_t)workspace & 15)) return ECORR_EINVAL;
+    if (!grad_weight != !grad_bias) return ECORR_EINVAL;
+    if (!grad_h && !grad_x && !grad_weight) return ECORR_EINVAL;   // nothing wanted
+    if (grad_weight)
+        for (int i = 0; i < 6; ++i)
+            if (!grad_weight[i] || !grad_bias[i]) return ECORR_EINVAL;
+    // every output disjoint from every input, both packs, the workspace and every other output: the kernels
+    // read h, x and the workspace while they write the outputs, and the outputs one after another
+    struct Region { const void* p; uintptr_t n; };
+    const uintptr_t n = (uintptr_t)B * H * W * 4, nw = (uintptr_t)hidden * (hidden + input) * 5 * 4;
+    Region in[6] = {{h, n * hidden}, {x, n * input}, {grad_out, n * hidden}, {packed, (uintptr_t)gru_packed_bytes()},
+                    {packed_t, (uintptr_t)gru_packed_t_bytes()},
+                    {workspace, (uintptr_t)gru_backward_workspace_bytes(B, H, W)}};
+    Region out[14];
+    int no = 0;
+    if (grad_h) out[no++] = {grad_h, n * hidden};
+    if (grad_x) out[no++] = {grad_x, n * input};
+    if (grad_weight)
+        for (int i = 0; i < 6; ++i) {
+            out[no++] = {grad_weight[i], nw};
+            out[no++] = {grad_bias[i], (uintptr_t)hidden * 4};
+        }
+    auto overlap = [](const Region& a, const Region& b) {
+        return (uintptr_t)a.p < (uintptr_t)b.p + b.n && (uintptr_t)b.p < (uintptr_t)a.p + a.n;
+    };
+    for (int i = 0; i < no; ++i) {
+        for (int k = 0; k < 6; ++k)
+            if (overlap(out[i], in[k])) return ECORR_EINVAL;
+        for (int k = 0; k < i; ++k)
+            if (overlap(out[i], out[k])) return ECORR_EINVAL;
+    }
+    // the workspace is written while h, x, grad_out and the packs are read
+    for (int k = 0; k < 5; ++k)
+        if (overlap(in[5], in[k])) return ECORR_EINVAL;
+    return launch_gru_backward(h, x, grad_out, B, H, W, packed, packed_t, grad_h, grad_x, grad_weight, grad_bias,
+                               workspace, (hipStream_t)stream);
+}
+
 ECORR_EXPORT int ecorr_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                                         int Hg, int Wg, float* out, float* mask, void* stream) {
     if (!img || !coords || !out || N <= 0 || C < 0 || h <= 0 || w <= 0 || Hg <= 0 || Wg <= 0)

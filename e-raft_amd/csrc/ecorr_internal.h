@@ -253,6 +253,17 @@ int64_t gru_workspace_bytes(int B, int H, int W);
 int launch_gru_pack(const float* const weight[6], const float* const bias[6], void* packed, hipStream_t stream);
 int launch_gru(const float* h, const float* x, int B, int H, int W, const void* packed, float* h_out, void* workspace,
                hipStream_t stream);
+// the forward with every gate kept, for the backward: g = [h1 z1 r1 q1 z2 r2 q2 h'] and rh, each [B][128][H W]
+int launch_gru_gates(const float* h, const float* x, int B, int H, int W, const void* packed, float* g, float* rh,
+                     hipStream_t stream);
+// gru_grad.hip: its backward (ecorr_sepconv_gru_backward*).  grad_h / grad_x may be null; grad_weight and
+// grad_bias (six pointers each, z1 r1 q1 z2 r2 q2) are both null or both complete.
+int64_t gru_packed_t_bytes();
+int64_t gru_backward_workspace_bytes(int B, int H, int W);
+int launch_gru_pack_t(const float* const weight[6], void* packed_t, hipStream_t stream);
+int launch_gru_backward(const float* h, const float* x, const float* grad_out, int B, int H, int W, const void* packed,
+                        const void* packed_t, float* grad_h, float* grad_x, float* const* grad_weight,
+                        float* const* grad_bias, void* workspace, hipStream_t stream);
 
 int launch_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                             int Hg, int Wg, float* out, float* mask, hipStream_t stream);

@@ -36,33 +36,18 @@
 //             p +- 1 of a row end is the next row, and p - W of row 0 is the previous channel's last
 //             row, both in range, so the range check alone would not give the zero padding.
 // No atomics: two runs give the same bits.
+//
+// launch_gru_gates is the same four launches with the kernels' SAVE flag, which also stores r and q: the gate
+// recompute of the backward (gru_grad.hip), whose h' is the forward's bit for bit.
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "gru_shape.h"
 #include "mfma_f32_frame.h"
 
 namespace ecorr {
 
 namespace {
-
-constexpr int GH = 128;            // hidden channels
-constexpr int GX = 256;            // input channels
-constexpr int GC = GH + GX;        // K channels per tap
-constexpr int GT = 5;              // taps
-constexpr int GKC = 16;            // channels per chunk (8 k-steps of v_mfma_f32_32x32x2_f32)
-constexpr int GNC = GC / GKC;      // chunks per tap
-constexpr int GNK = GT * GNC;      // chunks per GEMM
-constexpr int GFL = 12;            // chunks per first-level fmaf chain (192 products)
-constexpr int GNT = 256;           // threads (4 waves)
-static_assert(GNK % GFL == 0 && GH % GKC == 0, "whole chains; a chunk reads one tensor");
-
-constexpr int64_t kZrFloats = (int64_t)GNK * 2 * GH * GKC;   // packed floats of a z|r matrix (256 rows)
-constexpr int64_t kQFloats = (int64_t)GNK * GH * GKC;        // and of a q matrix (128 rows)
-constexpr int64_t kHalfFloats = kZrFloats + kQFloats;        // one half-step: z|r then q
-constexpr int64_t kPackFloats = 2 * kHalfFloats;             // then the 6 x 128 biases
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct GruTensors {
     const float* weight[6];   // z1 r1 q1 z2 r2 q2, each [128][384][5]
@@ -98,7 +83,9 @@ __global__ __launch_bounds__(GNT) void gru_pack_kernel(GruTensors T, float* __re
 
 // ZR (QK = false): in0 = h, outputs out0 = z, out1 = r * h.  Q (QK = true): in0 = r * h, zin = z,
 // hprev = h, output out0 = h'.  All of them [B][128][H W]; x [B][256][H W].
-template <int AXIS, bool QK>
+// SAVE (the backward's gate recompute, launch_gru_gates): the same arithmetic and the same stores, and the gate
+// itself is stored as well -- ZR: r at zin's address (zin is not read there), Q: q at out1.
+template <int AXIS, bool QK, bool SAVE = false>
 __global__ __launch_bounds__(GNT, 2) void gru_gemm_kernel(const float* __restrict__ in0, const float* __restrict__ x,
                                                        const float* __restrict__ packed,
                                                        const float* __restrict__ bias, int H, int W,
@@ -223,6 +210,7 @@ __global__ __launch_bounds__(GNT, 2) void gru_gemm_kernel(const float* __restric
                 const int64_t at = ib + (int64_t)o * HW;
                 const float z = zin[at], hp = hprev[at];
                 out0[at] = (1.0f - z) * hp + z * q;
+                if constexpr (SAVE) out1[at] = q;
             } else {
                 const float s = 1.0f / (1.0f + expf(-v));
                 if (rg == 0) {
@@ -230,6 +218,7 @@ __global__ __launch_bounds__(GNT, 2) void gru_gemm_kernel(const float* __restric
                 } else {
                     const int64_t at = ib + (int64_t)(o - GH) * HW;
                     out1[at] = s * hprev[at];
+                    if constexpr (SAVE) const_cast<float*>(zin)[at] = s;
                 }
             }
         }
@@ -277,6 +266,28 @@ int launch_gru(const float* h, const float* x, int B, int H, int W, const void* 
                        W, h1, nullptr, z, rh);
     hipLaunchKernelGGL((gru_gemm_kernel<1, true>), gq, dim3(GNT), 0, stream, rh, x, pk + kHalfFloats + kZrFloats,
                        bs + 5 * GH, H, W, h1, z, h_out, nullptr);
+    return hip_status();
+}
+
+// The forward again for the backward (gru_grad.hip), every gate kept: g = [h1 z1 r1 q1 z2 r2 q2 h'] and r * h
+// (of the half-step under way) in rh, each [B][128][H W].  The launches of launch_gru with SAVE: h' has its bits.
+int launch_gru_gates(const float* h, const float* x, int B, int H, int W, const void* packed, float* g, float* rh,
+                     hipStream_t stream) {
+    if (!gru_geometry_ok(B, H, W)) return ECORR_EINVAL;
+    const int HW = H * W;
+    const int64_t n = (int64_t)B * GH * HW;
+    float *h1 = g, *z1 = g + n, *r1 = g + 2 * n, *q1 = g + 3 * n, *z2 = g + 4 * n, *r2 = g + 5 * n, *q2 = g + 6 * n,
+          *ho = g + 7 * n;
+    const float* pk = (const float*)packed;
+    const float* bs = pk + kPackFloats;
+    const dim3 gzr((unsigned)((HW + 63) / 64), 1, (unsigned)B), gq((unsigned)((HW + 127) / 128), 1, (unsigned)B);
+    hipLaunchKernelGGL((gru_gemm_kernel<0, false, true>), gzr, dim3(GNT), 0, stream, h, x, pk, bs, H, W, h, r1, z1, rh);
+    hipLaunchKernelGGL((gru_gemm_kernel<0, true, true>), gq, dim3(GNT), 0, stream, rh, x, pk + kZrFloats, bs + 2 * GH,
+                       H, W, h, z1, h1, q1);
+    hipLaunchKernelGGL((gru_gemm_kernel<1, false, true>), gzr, dim3(GNT), 0, stream, h1, x, pk + kHalfFloats,
+                       bs + 3 * GH, H, W, h1, r2, z2, rh);
+    hipLaunchKernelGGL((gru_gemm_kernel<1, true, true>), gq, dim3(GNT), 0, stream, rh, x,
+                       pk + kHalfFloats + kZrFloats, bs + 5 * GH, H, W, h1, z2, ho, q2);
     return hip_status();
 }
 

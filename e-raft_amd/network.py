@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from .alt_corr import AlternateCorrBlock
 from .corr import CorrBlock
 from .flow import upsample_flow as hip_upsample_flow
-from .gru import sepconv_gru
+from .gru import sepconv_gru, sepconv_gru_train
 from .utils import coords_grid
 
 
@@ -148,9 +148,10 @@ class FlowHead(nn.Module):
 
 
 class BasicUpdateBlock(nn.Module):
-    def __init__(self, hidden_dim=128, corr_levels=4, corr_radius=4, hip_gru=False):
+    def __init__(self, hidden_dim=128, corr_levels=4, corr_radius=4, hip_gru=False, train_gru=False):
         super().__init__()
         self.hip_gru = bool(hip_gru)   # the GRU as eraft_amd.sepconv_gru on self.gru's weights (same keys)
+        self.train_gru = bool(train_gru)   # ... as eraft_amd.sepconv_gru_train: the same forward, with its HIP backward
         self.encoder = BasicMotionEncoder(corr_levels, corr_radius)
         self.gru = SepConvGRU(hidden_dim=hidden_dim, input_dim=128 + hidden_dim)
         self.flow_head = FlowHead(hidden_dim, hidden_dim=256)
@@ -159,7 +160,10 @@ class BasicUpdateBlock(nn.Module):
 
     def forward(self, net, inp, corr, flow, corr_is_convc1=False):
         inp = torch.cat([inp, self.encoder(flow, corr, corr_is_convc1)], dim=1)
-        net = sepconv_gru(net.contiguous(), inp, self.gru) if self.hip_gru else self.gru(net, inp)
+        if self.train_gru:
+            net = sepconv_gru_train(net.contiguous(), inp, self.gru)
+        else:
+            net = sepconv_gru(net.contiguous(), inp, self.gru) if self.hip_gru else self.gru(net, inp)
         return net, 0.25 * self.mask(net), self.flow_head(net)
 
 
@@ -225,6 +229,13 @@ class ERAFT(nn.Module):
     DESIGN.md §3.11) on the same parameters (the state_dict keys are unchanged): fp32 and forward-only.  It
     composes with fuse_motion_corr, hip_upsample and alternate_corr, and raises ValueError with
     mixed_precision, differentiable_corr, train_motion_corr or train_alternate_corr.
+    train_gru=True (keyword only) runs it as eraft_amd.sepconv_gru_train instead: the same forward launches (under
+    torch.no_grad() the predictions are bitwise hip_gru=True's) with the HIP backward of csrc/gru_grad.hip
+    (DESIGN.md §3.11.1), so a loss on the predictions trains the GRU's twelve parameters and everything in
+    front of it through native kernels.  It composes with differentiable_corr, train_motion_corr,
+    train_alternate_corr, fuse_motion_corr, hip_upsample and alternate_corr; hip_gru=True may be passed along and
+    changes nothing (its own refusals apply only without train_gru).  The kernels are fp32:
+    train_gru=True with mixed_precision=True raises ValueError.
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
@@ -233,9 +244,14 @@ class ERAFT(nn.Module):
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
                  differentiable_corr=False, train_motion_corr=False, mixed_precision=False,
                  amp_dtype=torch.float16, _native_half_lookup=True, *, alternate_corr=False,
-                 train_alternate_corr=False, hip_gru=False):
+                 train_alternate_corr=False, hip_gru=False, train_gru=False):
         super().__init__()
-        if hip_gru and (mixed_precision or differentiable_corr or train_motion_corr or train_alternate_corr):
+        if train_gru and mixed_precision:
+            raise ValueError("train_gru=True cannot be combined with mixed_precision: the HIP SepConvGRU and its "
+                             "backward are fp32")
+        self.train_gru = bool(train_gru)
+        if hip_gru and not train_gru and (mixed_precision or differentiable_corr or train_motion_corr or
+                                          train_alternate_corr):
             raise ValueError("hip_gru=True cannot be combined with mixed_precision, differentiable_corr, "
                              "train_motion_corr or train_alternate_corr: the HIP SepConvGRU is fp32 and forward-only")
         self.hip_gru = bool(hip_gru)
@@ -274,7 +290,7 @@ class ERAFT(nn.Module):
         self.cnet = BasicEncoder(output_dim=self.hidden_dim + self.context_dim, norm_fn="batch",
                                  dropout=0, n_first_channels=n_first_channels)
         self.update_block = BasicUpdateBlock(self.hidden_dim, self.corr_levels, self.corr_radius,
-                                             hip_gru=self.hip_gru)
+                                             hip_gru=self.hip_gru, train_gru=self.train_gru)
 
     def freeze_bn(self):
         """Keep every BatchNorm2d on its running statistics while the rest trains (eraft.py:60-63)."""

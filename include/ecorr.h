@@ -499,7 +499,7 @@ int ecorr_alt_pack_backward(float* grad_feat, int B, int D, int H, int W, int le
  * h float[B][hidden][H][W], x float[B][input][H][W], h_out float[B][hidden][H][W], contiguous fp32; h and x
  * are read in place (no concatenation).  Supported sizes: hidden = 128 and input = 256 only (the update
  * block's); every other (hidden, input) returns ECORR_EINVAL from all four entries.  H = 1 and W = 1 are
- * valid (every off-centre tap is then padding).  Forward only.
+ * valid (every off-centre tap is then padding).  Forward only (the gradients: ecorr_sepconv_gru_backward).
  * Arithmetic: the products run on the fp32 matrix instruction (exact fp32 operands, fp32 accumulation in
  * chains of 192 products that are then summed), sigmoid as 1 / (1 + expf(-v)), tanhf, the blend as two
  * products and a sum: within 1e-5 of an fp64 GRU, normwise (max |error| / rms).  No atomics: bitwise
@@ -527,6 +527,50 @@ int ecorr_sepconv_gru_pack(const float* const weight[6], const float* const bias
 int ecorr_sepconv_gru_workspace_size(int B, int hidden, int input, int H, int W, int64_t* bytes);
 int ecorr_sepconv_gru(const float* h, const float* x, int B, int hidden, int input, int H, int W,
                       const void* packed, float* h_out, void* workspace, void* stream);
+
+/* ---- SepConvGRU backward (four entries added within ABI 17: purely additive, the version stays 17) ----
+ * The gradients of ecorr_sepconv_gru (csrc/gru_grad.hip), first order, fp32, the same sizes (hidden = 128 and
+ * input = 256 only) and geometry limits.  Given h, x (the forward's inputs) and grad_out = dL/dh_out
+ * float[B][hidden][H][W], per half-step (the y half-step first, its grad_h is the x half-step's grad_out):
+ *   gq = g z (1 - q^2), gz = g (q - h) z (1 - z), [g_rh; gx_q] = conv_q^T(gq), gr = g_rh h r (1 - r),
+ *   [gh_zr; gx_zr] = conv_zr^T([gz; gr]), grad_h = g (1 - z) + g_rh r + gh_zr, grad_x = gx_q + gx_zr (summed
+ *   over both half-steps), grad_weight[o][c][t] = sum over batch items and pixels p of gpre[o][p] in[c][p + (t-2) e]
+ *   (valid shifted pixels only), grad_bias[o] = the sum of gpre[o][p].
+ * Nothing but h and x is kept from the forward: the call recomputes h1 and the six gates with the forward's
+ * kernels (the recomputed h_out is bitwise the forward's), so `packed` (ecorr_sepconv_gru_pack) is needed too.
+ * Outputs: grad_h float[B][hidden][H][W], grad_x float[B][input][H][W], each may be NULL (not wanted);
+ * grad_weight[i] float[hidden][hidden + input][5] and grad_bias[i] float[hidden], i in the order z1 r1 q1 z2
+ * r2 q2 (host arrays of six device pointers), both arrays NULL (a frozen GRU: the weight GEMMs are skipped) or
+ * both complete.  Every element of a wanted output is overwritten.
+ * Arithmetic: the fp32 matrix instruction; data gradients in chains of 160 products that are then summed,
+ * weight gradients in chains of at most 1024 pixels, summed per slab and then over the slabs in ascending
+ * order; a slab is a run of pixels of one batch item whose length depends on B, H and W alone.  No atomics:
+ * bitwise reproducible.
+ * Transposed pack: ecorr_sepconv_gru_backward_packed_size bytes = 4 * 6 * hidden * (hidden + input) * 5, 16-byte
+ * aligned, written once per weight set by ecorr_sepconv_gru_backward_pack (one launch).
+ * Workspace: ecorr_sepconv_gru_backward_workspace_size bytes, 16-byte aligned, no initialisation needed, contents
+ * undefined afterwards except as stated here.  With n = B * hidden * H * W * 4 bytes and P = H * W:
+ *   13 * n                                       h1 z1 r1 q1 z2 r2 q2 h_out' | r*h | gq | gz gr | grad_h1
+ *   + align256(B * ceil(P / 64) * 384 * 4)       bias partials
+ *   + B * nsl * 5 * 256 * 384 * 4                weight slab partials
+ * where cap = 1024, doubled while cap < P and B * ceil(P / cap) > 64; slab = ceil(ceil(P / ceil(P / cap)) / 32) * 32;
+ * nsl = ceil(P / slab); align256 rounds up to a multiple of 256.  After the call the first 8 * n bytes hold the
+ * recomputed h1, z1, r1, q1, z2, r2, q2 and h_out, each float[B][hidden][H][W].
+ * ecorr_sepconv_gru_backward: stream-ordered launches on `stream`, no host synchronisation, no allocation.
+ * Errors (before any GPU call), all ECORR_EINVAL: those of ecorr_sepconv_gru (sizes, geometry, null h, x,
+ * packed, workspace; misaligned packed or workspace), a null grad_out or packed_t, a misaligned packed_t, all
+ * of grad_h, grad_x and grad_weight NULL, exactly one of grad_weight and grad_bias NULL, a NULL entry in
+ * either array, an output overlapping h, x, grad_out, a pack, the workspace or another output, and the
+ * workspace overlapping h, x, grad_out or a pack. */
+int ecorr_sepconv_gru_backward_packed_size(int hidden, int input, int64_t* bytes);
+int ecorr_sepconv_gru_backward_pack(const float* const weight[6], int hidden, int input, void* packed_t, void* stream);
+int ecorr_sepconv_gru_backward_workspace_size(int B, int hidden, int input, int H, int W, int64_t* bytes);
+int ecorr_sepconv_gru_backward(const float* h, const float* x, const float* grad_out,
+                               int B, int hidden, int input, int H, int W,
+                               const void* packed, const void* packed_t,
+                               float* grad_h, float* grad_x,
+                               float* const grad_weight[6], float* const grad_bias[6],
+                               void* workspace, void* stream);
 
 /* Tile shape of the pyramid storage (ECORR_TILE_H, ECORR_TILE_W). */
 int ecorr_pyramid_tile(int* tile_h, int* tile_w);
