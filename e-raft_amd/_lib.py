@@ -135,6 +135,12 @@ SYMBOLS = {
     "ecorr_sepconv_gru_backward_workspace_size": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i64)]),
     "ecorr_sepconv_gru_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, ctypes.POINTER(_p),
                                         ctypes.POINTER(_p), _p, _p]),
+    # the motion encoder behind convc1 (added within ABI 17): (bytes*) / (weight[4], bias[4], packed, stream) /
+    # (B, H, W, bytes*) / (c1, flow, B, H, W, packed, out, out_batch_stride, workspace, stream)
+    "ecorr_motion_encoder_packed_size": (_i, [ctypes.POINTER(_i64)]),
+    "ecorr_motion_encoder_pack": (_i, [ctypes.POINTER(_p), ctypes.POINTER(_p), _p, _p]),
+    "ecorr_motion_encoder_workspace_size": (_i, [_i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_motion_encoder": (_i, [_p, _p, _i, _i, _i, _p, _p, _i64, _p, _p]),
     "ecorr_bilinear_sampler": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
     "ecorr_coords_grid": (_i, [_i, _i, _i, _p, _p]),
     # (chunks, chunk, world, B, C, H, W, out, stream)

@@ -689,6 +689,47 @@ ECORR_EXPORT int ecorr_sepconv_gru_backward(const float* h, const float* x, cons
                                workspace, (hipStream_t)stream);
 }
 
+ECORR_EXPORT int ecorr_motion_encoder_packed_size(int64_t* bytes) {
+    if (!bytes) return ECORR_EINVAL;
+    *bytes = menc_packed_bytes();
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_motion_encoder_pack(const float* const weight[4], const float* const bias[4], void* packed,
+                                           void* stream) {
+    if (!weight || !bias || !packed || ((uintptr_t)packed & 15)) return ECORR_EINVAL;
+    for (int i = 0; i < 4; ++i)
+        if (!weight[i] || !bias[i]) return ECORR_EINVAL;
+    return launch_menc_pack(weight, bias, packed, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_motion_encoder_workspace_size(int B, int H, int W, int64_t* bytes) {
+    if (!bytes || !menc_geometry_ok(B, H, W)) return ECORR_EINVAL;
+    *bytes = menc_workspace_bytes(B, H, W);
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_motion_encoder(const float* c1, const float* flow, int B, int H, int W, const void* packed,
+                                      float* out, int64_t out_batch_stride, void* workspace, void* stream) {
+    if (!c1 || !flow || !packed || !out || !workspace || !menc_geometry_ok(B, H, W)) return ECORR_EINVAL;
+    if (((uintptr_t)packed & 15) || ((uintptr_t)workspace & 15)) return ECORR_EINVAL;
+    const int64_t hw = (int64_t)H * W;
+    if (out_batch_stride < 128 * hw || out_batch_stride > (int64_t)1 << 40) return ECORR_EINVAL;
+    // out's whole strided extent (the gaps between its batch items included) disjoint from everything the
+    // launches read, and the workspace (cor, f1, flo: written and read back) from the inputs and the pack
+    auto overlap = [](const void* a, uintptr_t na, const void* b, uintptr_t nb) {
+        return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+    };
+    const uintptr_t n = (uintptr_t)B * hw * 4, nc1 = n * 256, nfl = n * 2;
+    const uintptr_t nout = ((uintptr_t)(B - 1) * out_batch_stride + 128 * hw) * 4;
+    const uintptr_t nws = (uintptr_t)menc_workspace_bytes(B, H, W), npk = (uintptr_t)menc_packed_bytes();
+    if (overlap(out, nout, c1, nc1) || overlap(out, nout, flow, nfl) || overlap(out, nout, packed, npk) ||
+        overlap(out, nout, workspace, nws) || overlap(workspace, nws, c1, nc1) || overlap(workspace, nws, flow, nfl) ||
+        overlap(workspace, nws, packed, npk))
+        return ECORR_EINVAL;
+    return launch_menc(c1, flow, B, H, W, packed, out, out_batch_stride, workspace, (hipStream_t)stream);
+}
+
 ECORR_EXPORT int ecorr_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                                         int Hg, int Wg, float* out, float* mask, void* stream) {
     if (!img || !coords || !out || N <= 0 || C < 0 || h <= 0 || w <= 0 || Hg <= 0 || Wg <= 0)

@@ -265,6 +265,15 @@ int launch_gru_backward(const float* h, const float* x, const float* grad_out, i
                         const void* packed_t, float* grad_h, float* grad_x, float* const* grad_weight,
                         float* const* grad_bias, void* workspace, hipStream_t stream);
 
+// motion_enc.hip: the motion encoder behind convc1 (ecorr_motion_encoder*, include/ecorr.h).  weight / bias in the
+// order convc2 convf1 convf2 conv; out [b] at out + b out_batch_stride floats, [128][H W].
+bool menc_geometry_ok(int B, int H, int W);
+int64_t menc_packed_bytes();
+int64_t menc_workspace_bytes(int B, int H, int W);
+int launch_menc_pack(const float* const weight[4], const float* const bias[4], void* packed, hipStream_t stream);
+int launch_menc(const float* c1, const float* flow, int B, int H, int W, const void* packed, float* out,
+                int64_t out_batch_stride, void* workspace, hipStream_t stream);
+
 int launch_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                             int Hg, int Wg, float* out, float* mask, hipStream_t stream);
 

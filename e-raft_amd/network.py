@@ -25,6 +25,7 @@ from .alt_corr import AlternateCorrBlock
 from .corr import CorrBlock
 from .flow import upsample_flow as hip_upsample_flow
 from .gru import sepconv_gru, sepconv_gru_train
+from .motion_enc import motion_encoder
 from .utils import coords_grid
 
 
@@ -158,8 +159,10 @@ class BasicUpdateBlock(nn.Module):
         self.mask = nn.Sequential(nn.Conv2d(128, 256, 3, padding=1), nn.ReLU(inplace=True),
                                   nn.Conv2d(256, 64 * 9, 1, padding=0))
 
-    def forward(self, net, inp, corr, flow, corr_is_convc1=False):
-        inp = torch.cat([inp, self.encoder(flow, corr, corr_is_convc1)], dim=1)
+    def forward(self, net, inp, corr, flow, corr_is_convc1=False, x=None):
+        # x: the GRU's input [inp, motion features] already assembled (ERAFT hip_motion_encoder=True: inp once,
+        # eraft_amd.motion_encoder into its upper half every iteration); inp, corr and flow are then not read
+        inp = torch.cat([inp, self.encoder(flow, corr, corr_is_convc1)], dim=1) if x is None else x
         if self.train_gru:
             net = sepconv_gru_train(net.contiguous(), inp, self.gru)
         else:
@@ -236,6 +239,14 @@ class ERAFT(nn.Module):
     train_alternate_corr, fuse_motion_corr, hip_upsample and alternate_corr; hip_gru=True may be passed along and
     changes nothing (its own refusals apply only without train_gru).  The kernels are fp32:
     train_gru=True with mixed_precision=True raises ValueError.
+    hip_motion_encoder=True (keyword only) runs what BasicMotionEncoder does behind convc1 -- convc2, convf1, convf2,
+    conv and both concatenations -- as eraft_amd.motion_encoder (csrc/motion_enc.hip) on the same
+    parameters (the state_dict keys are unchanged): the GRU's input x [B, 256, H/8, W/8] is allocated once per
+    forward with the context features in its lower half, and every iteration the kernels write the motion
+    features into its upper half, so neither torch.cat runs.  relu(convc1(corr)) comes from
+    CorrBlock.lookup_conv1x1_relu under fuse_motion_corr, else from the lookup and torch's convc1.  fp32 and
+    forward-only: it composes with fuse_motion_corr, hip_upsample, hip_gru and alternate_corr, and raises ValueError
+    with mixed_precision, differentiable_corr, train_motion_corr, train_alternate_corr or train_gru.
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
@@ -244,8 +255,14 @@ class ERAFT(nn.Module):
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
                  differentiable_corr=False, train_motion_corr=False, mixed_precision=False,
                  amp_dtype=torch.float16, _native_half_lookup=True, *, alternate_corr=False,
-                 train_alternate_corr=False, hip_gru=False, train_gru=False):
+                 train_alternate_corr=False, hip_gru=False, train_gru=False, hip_motion_encoder=False):
         super().__init__()
+        if hip_motion_encoder and (mixed_precision or differentiable_corr or train_motion_corr or
+                                   train_alternate_corr or train_gru):
+            raise ValueError("hip_motion_encoder=True cannot be combined with mixed_precision, differentiable_corr, "
+                             "train_motion_corr, train_alternate_corr or train_gru: the HIP motion encoder is fp32 "
+                             "and forward-only")
+        self.hip_motion_encoder = bool(hip_motion_encoder)
         if train_gru and mixed_precision:
             raise ValueError("train_gru=True cannot be combined with mixed_precision: the HIP SepConvGRU and its "
                              "backward are fp32")
@@ -347,19 +364,32 @@ class ERAFT(nn.Module):
         if flow_init is not None:
             coords1 = coords1 + flow_init
         predictions = []
+        if self.hip_motion_encoder:   # the GRU's input, assembled in place: inp once, the motion features per iteration
+            x = torch.empty((inp.shape[0], self.context_dim + 128) + tuple(inp.shape[2:]), dtype=torch.float32,
+                            device=inp.device)
+            x[:, :self.context_dim].copy_(inp)
         for _ in range(iters):
             coords1 = coords1.detach()
-            if self.fuse_motion_corr:
-                c1 = self.update_block.encoder.convc1
-                corr = corr_fn.lookup_conv1x1_relu(coords1, c1.weight, c1.bias,
-                                                   **({"out_dtype": self.amp_dtype} if half_lookup else {}))
-            elif half_lookup:
-                corr = corr_fn(coords1, out_dtype=self.amp_dtype)
+            if self.hip_motion_encoder:   # fp32, no autocast: the constructor refuses mixed_precision
+                enc = self.update_block.encoder
+                if self.fuse_motion_corr:
+                    c1 = corr_fn.lookup_conv1x1_relu(coords1, enc.convc1.weight, enc.convc1.bias)
+                else:
+                    c1 = F.relu(enc.convc1(corr_fn(coords1)))
+                motion_encoder(coords1 - coords0, c1.contiguous(), enc, out=x[:, self.context_dim:])
+                net, up_mask, delta = self.update_block(net, None, None, None, x=x)
             else:
-                corr = corr_fn(coords1)
-            with self._autocast():
-                net, up_mask, delta = self.update_block(net, inp, corr, coords1 - coords0,
-                                                        corr_is_convc1=self.fuse_motion_corr)
+                if self.fuse_motion_corr:
+                    c1 = self.update_block.encoder.convc1
+                    corr = corr_fn.lookup_conv1x1_relu(coords1, c1.weight, c1.bias,
+                                                       **({"out_dtype": self.amp_dtype} if half_lookup else {}))
+                elif half_lookup:
+                    corr = corr_fn(coords1, out_dtype=self.amp_dtype)
+                else:
+                    corr = corr_fn(coords1)
+                with self._autocast():
+                    net, up_mask, delta = self.update_block(net, inp, corr, coords1 - coords0,
+                                                            corr_is_convc1=self.fuse_motion_corr)
             coords1 = coords1 + delta
             if self.hip_upsample:   # the HIP kernel takes fp32 (autocast's mask is amp_dtype)
                 up = hip_upsample_flow(coords1 - coords0, up_mask.float())

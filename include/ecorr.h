@@ -572,6 +572,45 @@ int ecorr_sepconv_gru_backward(const float* h, const float* x, const float* grad
                                float* const grad_weight[6], float* const grad_bias[6],
                                void* workspace, void* stream);
 
+/* ---- Motion encoder (four entries added within ABI 17: purely additive, the version stays 17) ----
+ * BasicMotionEncoder behind convc1 (model/update.py:68-81, csrc/motion_enc.hip), zero padding throughout:
+ *   cor = relu(convc2(c1))  3x3, 256 -> 192      f1  = relu(convf1(flow))  7x7, 2 -> 128
+ *   flo = relu(convf2(f1))  3x3, 128 -> 64       out = [relu(conv([cor, flo])), flow]  3x3, 256 -> 126, then flow's 2
+ * c1 float[B][256][H][W] = relu(convc1(corr)) (ecorr_lookup_conv1x1_relu*, or any producer), flow float[B][2][H][W],
+ * both contiguous fp32 and only read.  out: batch item b is float[128][H][W] at out + b * out_batch_stride (in
+ * floats, >= 128 * H * W), so out may be the upper half of the GRU's x float[B][256][H][W] (out = x + 128 * H * W,
+ * out_batch_stride = 256 * H * W) and neither concatenation runs.  H = 1 and W = 1 are valid (every off-centre
+ * tap is then padding).  Forward only.
+ * Arithmetic: the three 3x3 convolutions run on the fp32 matrix instruction (exact fp32 operands, fp32
+ * accumulation in chains of 192 products -- 12 chains for convc2 and conv, 6 for convf2 -- that are then summed),
+ * convf1 as one k-ordered fmaf chain of 98 products; the bias is added last; relu is v < 0 ? 0 : v: within 1e-5 of
+ * an fp64 encoder on channels 0-125, normwise (max |error| / rms).  Channels 126 and 127 of out are flow, copied
+ * bit for bit.  No atomics: bitwise reproducible, and a batch item's result does not depend on B.
+ * Non-finite values: relu keeps a NaN (as torch.relu does), and there is no shared exponent to spread one: a NaN
+ * in c1 makes channels 0-125 NaN on the 5 x 5 block around its pixel (two 3x3 convolutions), a NaN in flow on the
+ * 11 x 11 block (7x7, then two 3x3) and in its own flow channel at its own pixel, each clipped to the image and
+ * within its own batch item -- the reference's footprint, nothing more.  +-inf behaves as in an fp32
+ * convolution (inf * 0 weight = NaN).
+ * Packed weights: ecorr_motion_encoder_packed_size bytes = 4 * (9 * 256 * 192 + 9 * 128 * 64 + 9 * 256 * 128 +
+ * 128 * 100 + 512) = 3297280 (convc2, convf2 and conv with its 126 rows padded to 128 by zero rows, convf1's rows of
+ * 98 padded to 100, the biases 192 + 128 + 64 + 128), 16-byte aligned; written once per weight set by
+ * ecorr_motion_encoder_pack (one launch).  weight and bias are host arrays of four device pointers.
+ * Workspace: ecorr_motion_encoder_workspace_size bytes = 384 * B * H * W * 4 (cor, f1 and flo), 16-byte aligned;
+ * it needs no initialisation and its contents are undefined afterwards.
+ * ecorr_motion_encoder: four launches on `stream`, no host synchronisation, no allocation.
+ * Errors (before any GPU call), all ECORR_EINVAL: a null pointer (an array entry included), a packed buffer or
+ * workspace that is not 16-byte aligned, B, H or W < 1, B > 65535, 256 * H * W * 4 beyond 2^31 - 1 (H * W >
+ * 2097151: the buffer range of the kernels' 32-bit offsets within one batch item; the batch offsets are 64-bit),
+ * out_batch_stride < 128 * H * W (or beyond 2^40), out's whole strided extent ((B - 1) * out_batch_stride +
+ * 128 * H * W floats) overlapping c1, flow, the pack or the workspace, and the workspace overlapping c1, flow or
+ * the pack.  c1 and flow may share memory with each other or with the pack. */
+int ecorr_motion_encoder_packed_size(int64_t* bytes);
+int ecorr_motion_encoder_pack(const float* const weight[4], const float* const bias[4], void* packed, void* stream);
+        /* order: convc2 convf1 convf2 conv; weight shapes [192][256][3][3] [128][2][7][7] [64][128][3][3] [126][256][3][3] */
+int ecorr_motion_encoder_workspace_size(int B, int H, int W, int64_t* bytes);
+int ecorr_motion_encoder(const float* c1, const float* flow, int B, int H, int W, const void* packed,
+                         float* out, int64_t out_batch_stride, void* workspace, void* stream);
+
 /* Tile shape of the pyramid storage (ECORR_TILE_H, ECORR_TILE_W). */
 int ecorr_pyramid_tile(int* tile_h, int* tile_w);
 
