@@ -16,9 +16,9 @@ from .image_utils import forward_interpolate_pytorch, grid_sample_values
 from .flow import flow_16bit_to_float, flow_to_png16, upsample_flow
 from .voxel import EventSequenceToVoxelGrid_Pytorch, VoxelGrid
 from .gru import sepconv_gru, sepconv_gru_train
-from .motion_enc import motion_encoder
+from .motion_enc import motion_encoder, motion_encoder_train
 from ._lib import LIB_PATH, lib
 
 __all__ = ["CorrBlock", "AlternateCorrBlock", "bilinear_sampler", "coords_grid", "forward_interpolate_pytorch",
            "grid_sample_values", "upsample_flow", "flow_to_png16", "flow_16bit_to_float", "sepconv_gru",
-           "sepconv_gru_train", "motion_encoder", "VoxelGrid", "EventSequenceToVoxelGrid_Pytorch", "LIB_PATH", "lib"]
+           "sepconv_gru_train", "motion_encoder", "motion_encoder_train", "VoxelGrid", "EventSequenceToVoxelGrid_Pytorch", "LIB_PATH", "lib"]

@@ -141,6 +141,14 @@ SYMBOLS = {
     "ecorr_motion_encoder_pack": (_i, [ctypes.POINTER(_p), ctypes.POINTER(_p), _p, _p]),
     "ecorr_motion_encoder_workspace_size": (_i, [_i, _i, _i, ctypes.POINTER(_i64)]),
     "ecorr_motion_encoder": (_i, [_p, _p, _i, _i, _i, _p, _p, _i64, _p, _p]),
+    # its backward (added within ABI 17): (bytes*) / (weight[4], packed_t, stream) / (B, H, W, bytes*) / (c1, flow,
+    # grad_out, grad_out_batch_stride, B, H, W, packed, packed_t, grad_c1, grad_flow, grad_weight[4], grad_bias[4],
+    # workspace, stream)
+    "ecorr_motion_encoder_backward_packed_size": (_i, [ctypes.POINTER(_i64)]),
+    "ecorr_motion_encoder_backward_pack": (_i, [ctypes.POINTER(_p), _p, _p]),
+    "ecorr_motion_encoder_backward_workspace_size": (_i, [_i, _i, _i, ctypes.POINTER(_i64)]),
+    "ecorr_motion_encoder_backward": (_i, [_p, _p, _p, _i64, _i, _i, _i, _p, _p, _p, _p, ctypes.POINTER(_p),
+                                           ctypes.POINTER(_p), _p, _p]),
     "ecorr_bilinear_sampler": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
     "ecorr_coords_grid": (_i, [_i, _i, _i, _p, _p]),
     # (chunks, chunk, world, B, C, H, W, out, stream)

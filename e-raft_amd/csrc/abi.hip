@@ -730,6 +730,73 @@ ECORR_EXPORT int ecorr_motion_encoder(const float* c1, const float* flow, int B,
     return launch_menc(c1, flow, B, H, W, packed, out, out_batch_stride, workspace, (hipStream_t)stream);
 }
 
+ECORR_EXPORT int ecorr_motion_encoder_backward_packed_size(int64_t* bytes) {
+    if (!bytes) return ECORR_EINVAL;
+    *bytes = menc_packed_t_bytes();
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_motion_encoder_backward_pack(const float* const weight[4], void* packed_t, void* stream) {
+    if (!weight || !packed_t || ((uintptr_t)packed_t & 15)) return ECORR_EINVAL;
+    for (int i = 0; i < 4; ++i)
+        if (!weight[i]) return ECORR_EINVAL;
+    return launch_menc_pack_t(weight, packed_t, (hipStream_t)stream);
+}
+
+ECORR_EXPORT int ecorr_motion_encoder_backward_workspace_size(int B, int H, int W, int64_t* bytes) {
+    if (!bytes || !menc_geometry_ok(B, H, W)) return ECORR_EINVAL;
+    *bytes = menc_backward_workspace_bytes(B, H, W);
+    return ECORR_OK;
+}
+
+ECORR_EXPORT int ecorr_motion_encoder_backward(const float* c1, const float* flow, const float* grad_out,
+                                               int64_t grad_out_batch_stride, int B, int H, int W, const void* packed,
+                                               const void* packed_t, float* grad_c1, float* grad_flow,
+                                               float* const grad_weight[4], float* const grad_bias[4], void* workspace,
+                                               void* stream) {
+    if (!c1 || !flow || !grad_out || !packed || !packed_t || !workspace || !menc_geometry_ok(B, H, W))
+        return ECORR_EINVAL;
+    if (((uintptr_t)packed & 15) || ((uintptr_t)packed_t & 15) || ((uintptr_t)workspace & 15)) return ECORR_EINVAL;
+    const int64_t hw = (int64_t)H * W;
+    if (grad_out_batch_stride < 128 * hw || grad_out_batch_stride > (int64_t)1 << 40) return ECORR_EINVAL;
+    if (!grad_weight != !grad_bias) return ECORR_EINVAL;
+    if (!grad_c1 && !grad_flow && !grad_weight) return ECORR_EINVAL;   // nothing wanted
+    if (grad_weight)
+        for (int i = 0; i < 4; ++i)
+            if (!grad_weight[i] || !grad_bias[i]) return ECORR_EINVAL;
+    // every output disjoint from every input (grad_out's whole strided extent, the gaps between its batch items
+    // included), both packs, the workspace and every other output; the workspace from what is read while it is written
+    struct Region { const void* p; uintptr_t n; };
+    const uintptr_t n = (uintptr_t)B * hw * 4;
+    static const uintptr_t wn[4] = {192 * 256 * 9, 128 * 2 * 49, 64 * 128 * 9, 126 * 256 * 9}, bn[4] = {192, 128, 64, 126};
+    Region in[6] = {{c1, n * 256}, {flow, n * 2},
+                    {grad_out, ((uintptr_t)(B - 1) * grad_out_batch_stride + 128 * hw) * 4},
+                    {packed, (uintptr_t)menc_packed_bytes()}, {packed_t, (uintptr_t)menc_packed_t_bytes()},
+                    {workspace, (uintptr_t)menc_backward_workspace_bytes(B, H, W)}};
+    Region out[10];
+    int no = 0;
+    if (grad_c1) out[no++] = {grad_c1, n * 256};
+    if (grad_flow) out[no++] = {grad_flow, n * 2};
+    if (grad_weight)
+        for (int i = 0; i < 4; ++i) {
+            out[no++] = {grad_weight[i], wn[i] * 4};
+            out[no++] = {grad_bias[i], bn[i] * 4};
+        }
+    auto overlap = [](const Region& a, const Region& b) {
+        return (uintptr_t)a.p < (uintptr_t)b.p + b.n && (uintptr_t)b.p < (uintptr_t)a.p + a.n;
+    };
+    for (int i = 0; i < no; ++i) {
+        for (int k = 0; k < 6; ++k)
+            if (overlap(out[i], in[k])) return ECORR_EINVAL;
+        for (int k = 0; k < i; ++k)
+            if (overlap(out[i], out[k])) return ECORR_EINVAL;
+    }
+    for (int k = 0; k < 5; ++k)
+        if (overlap(in[5], in[k])) return ECORR_EINVAL;
+    return launch_menc_backward(c1, flow, grad_out, grad_out_batch_stride, B, H, W, packed, packed_t, grad_c1, grad_flow,
+                                grad_weight, grad_bias, workspace, (hipStream_t)stream);
+}
+
 ECORR_EXPORT int ecorr_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                                         int Hg, int Wg, float* out, float* mask, void* stream) {
     if (!img || !coords || !out || N <= 0 || C < 0 || h <= 0 || w <= 0 || Hg <= 0 || Wg <= 0)

@@ -273,6 +273,19 @@ int64_t menc_workspace_bytes(int B, int H, int W);
 int launch_menc_pack(const float* const weight[4], const float* const bias[4], void* packed, hipStream_t stream);
 int launch_menc(const float* c1, const float* flow, int B, int H, int W, const void* packed, float* out,
                 int64_t out_batch_stride, void* workspace, hipStream_t stream);
+// the forward's first three launches into cor [B][192][H W], f1 [B][128][H W] and flo [B][64][H W], then conv's GEMM
+// writing go = relu'(conv's result) grad_out[:126] (two zero rows behind) [B][128][H W] instead of the result;
+// grad_out item b at grad_out + b grad_out_bs
+int launch_menc_recompute(const float* c1, const float* flow, const float* grad_out, int64_t grad_out_bs, int B, int H,
+                          int W, const void* packed, float* cor, float* f1, float* flo, float* go, hipStream_t stream);
+// motion_enc_grad.hip: its backward (ecorr_motion_encoder_backward*).  grad_c1 / grad_flow may be null; grad_weight
+// and grad_bias (four pointers each, convc2 convf1 convf2 conv) are both null or both complete.
+int64_t menc_packed_t_bytes();
+int64_t menc_backward_workspace_bytes(int B, int H, int W);
+int launch_menc_pack_t(const float* const weight[4], void* packed_t, hipStream_t stream);
+int launch_menc_backward(const float* c1, const float* flow, const float* grad_out, int64_t grad_out_bs, int B, int H,
+                         int W, const void* packed, const void* packed_t, float* grad_c1, float* grad_flow,
+                         float* const* grad_weight, float* const* grad_bias, void* workspace, hipStream_t stream);
 
 int launch_bilinear_sampler(const float* img, int N, int C, int h, int w, const float* coords,
                             int Hg, int Wg, float* out, float* mask, hipStream_t stream);

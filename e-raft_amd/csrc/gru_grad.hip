@@ -35,6 +35,7 @@
 
 #include "ecorr_device.h"
 #include "ecorr_internal.h"
+#include "grad_slab.h"   // gru_grad_slab
 #include "gru_shape.h"
 #include "mfma_f32_frame.h"
 
@@ -52,9 +53,8 @@ constexpr int64_t kQTFloats = (int64_t)3 * kNkQ * DCH;     // transposed q matri
 constexpr int64_t kHalfTFloats = kZrTFloats + kQTFloats;
 constexpr int64_t kPackTFloats = 2 * kHalfTFloats;
 
-constexpr int WK = kFrameK;              // weight gradient: pixels per chunk
-constexpr int kChain = 1024;             // ... and per first-level chain
-constexpr int kSlabs = 64;               // the slab cap doubles while a launch would have more slabs than this
+constexpr int WK = kGradWK;              // weight gradient: pixels per chunk
+constexpr int kChain = kGradChain;       // ... and per first-level chain (grad_slab.h)
 constexpr int BQ = 64;                   // bias partials: pixels per workgroup
 
 struct GruGradLayout {
@@ -65,16 +65,6 @@ struct GruGradLayout {
 };
 
 int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-// slabs of the weight gradient's pixel reduction, within one batch item: a cap of 1024 pixels, doubled while
-// the launch would have more than 64 slabs, then balanced slabs of whole chunks under the cap
-void gru_grad_slab(int B, int HW, int* nsl, int* slab) {
-    int64_t cap = kChain;
-    while (cap < HW && (int64_t)B * ((HW + cap - 1) / cap) > kSlabs) cap *= 2;
-    const int64_t per = (HW + cap - 1) / cap;
-    *slab = (int)(((HW + per - 1) / per + WK - 1) / WK * WK);
-    *nsl = (HW + *slab - 1) / *slab;
-}
 
 GruGradLayout gru_grad_layout(int B, int H, int W) {
     GruGradLayout L;

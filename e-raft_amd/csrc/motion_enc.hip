@@ -129,7 +129,10 @@ __global__ __launch_bounds__(MENT) void menc_convf1_kernel(const float* __restri
 // out[o][p] = relu(bias[o] + sum over taps t and channels c of W[o][c][t] in[c][p shifted by t]), in = [in0 | in1]
 // of C0 and C1 channels ([B][C0][H W] and [B][C1][H W]; in1 unused when C1 = 0); out [b] at out + b out_bs,
 // [M][H W].  FLOW: rows 126 and 127 are flow's ([B][2][H W]) instead.
-template <int M, int C0, int C1, bool FLOW>
+// GO (the backward's recompute of conv, launch_menc_recompute): nothing of the result is stored; `flow` is
+// grad_out, item b at flow + b out_bs, and out [B][M][H W] gets go = relu'(result) grad_out on rows 0-125 -- the
+// result <= 0 ? 0 : g of torch's threshold_backward: a NaN result passes g -- and 0 on rows 126 and 127.
+template <int M, int C0, int C1, bool FLOW, bool GO = false>
 __global__ __launch_bounds__(MENT, 2) void menc_gemm_kernel(const float* __restrict__ in0, const float* __restrict__ in1,
                                                           const float* __restrict__ packed,
                                                           const float* __restrict__ bias, int H, int W,
@@ -249,6 +252,23 @@ __global__ __launch_bounds__(MENT, 2) void menc_gemm_kernel(const float* __restr
 
     // ---- epilogue: lane holds pixel p, rows 32 rb + mfma_c_row(r, kh)
     if (!pok) return;
+    if constexpr (GO) {
+        const float* gb = flow + (int64_t)b * out_bs + p;
+        float* gob = out + (int64_t)b * M * HW + p;
+#pragma unroll
+        for (int i = 0; i < RBW; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int o = 32 * (RBW * rg + i) + mfma_c_row(r, kh);
+                float v = 0.0f;
+                if (o < MECONV) {
+                    const float y = menc_relu(tot[i][r] + bias[o]);
+                    v = y <= 0.0f ? 0.0f : gb[(int64_t)o * HW];
+                }
+                gob[(int64_t)o * HW] = v;
+            }
+        return;
+    }
     float* ob = out + (int64_t)b * out_bs + p;
 #pragma unroll
     for (int i = 0; i < RBW; ++i)
@@ -302,6 +322,26 @@ int launch_menc(const float* c1, const float* flow, int B, int H, int W, const v
                        pk + kMeF2At, bs + kMeBiasF2, H, W, nullptr, flo, (int64_t)MEFLO * HW);
     hipLaunchKernelGGL((menc_gemm_kernel<MEOUT, MECOR, MEFLO, true>), g128, dim3(MENT), 0, stream, cor, flo,
                        pk + kMeCvAt, bs + kMeBiasCv, H, W, flow, out, out_batch_stride);
+    return hip_status();
+}
+
+// The backward's recompute (motion_enc_grad.hip): launch_menc's first three launches into cor, f1 and flo, then
+// conv's GEMM with the GO epilogue: go [B][128][H W] from grad_out (item b at grad_out + b grad_out_bs); conv's
+// own result is never stored.
+int launch_menc_recompute(const float* c1, const float* flow, const float* grad_out, int64_t grad_out_bs, int B, int H,
+                          int W, const void* packed, float* cor, float* f1, float* flo, float* go, hipStream_t stream) {
+    if (!menc_geometry_ok(B, H, W)) return ECORR_EINVAL;
+    const int HW = H * W;
+    const float* pk = (const float*)packed;
+    const float* bs = pk + kMeBiasAt;
+    const dim3 g64((unsigned)((HW + 63) / 64), 1, (unsigned)B), g128((unsigned)((HW + 127) / 128), 1, (unsigned)B);
+    hipLaunchKernelGGL(menc_convf1_kernel, g64, dim3(MENT), 0, stream, flow, pk + kMeF1At, bs + kMeBiasF1, H, W, f1);
+    hipLaunchKernelGGL((menc_gemm_kernel<MECOR, MEC1, 0, false>), g64, dim3(MENT), 0, stream, c1, nullptr,
+                       pk + kMeC2At, bs + kMeBiasC2, H, W, nullptr, cor, (int64_t)MECOR * HW);
+    hipLaunchKernelGGL((menc_gemm_kernel<MEFLO, MEF1, 0, false>), g128, dim3(MENT), 0, stream, f1, nullptr,
+                       pk + kMeF2At, bs + kMeBiasF2, H, W, nullptr, flo, (int64_t)MEFLO * HW);
+    hipLaunchKernelGGL((menc_gemm_kernel<MEOUT, MECOR, MEFLO, false, true>), g128, dim3(MENT), 0, stream, cor, flo,
+                       pk + kMeCvAt, bs + kMeBiasCv, H, W, grad_out, go, grad_out_bs);
     return hip_status();
 }
 

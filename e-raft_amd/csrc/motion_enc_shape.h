@@ -36,4 +36,23 @@ constexpr int kMeBiasFloats = kMeBiasCv + MEOUT;
 constexpr int64_t kMePackFloats = kMeBiasAt + kMeBiasFloats;
 static_assert(kMeF2At % 4 == 0 && kMeCvAt % 4 == 0 && kMeF1At % 4 == 0 && kMePackFloats % 4 == 0, "16-byte pieces");
 
+// The backward (motion_enc_grad.hip).  The transposed, tap-flipped pack: conv^T (256 rows [cor | flo], K = 9 x 128:
+// go's 126 rows and two zero rows), convc2^T (256 rows, K = 9 x 192), convf2^T (128 rows, K = 9 x 64); a matrix is
+// rows / 128 row groups of 9 K / 16 chunks (tap-major) of 128 x 16 floats.  convf1 has no transposed pack: its data
+// gradient reads the forward pack's rows.
+constexpr int MEDR = 128;                          // rows per workgroup (and row group) of a data gradient
+constexpr int MEDCH = MEDR * MEKC;                 // floats of one (row group, chunk)
+constexpr int64_t kMeTCvFloats = (int64_t)MET * (MECOR + MEFLO) * MEOUT;   // 2 x 72 chunks
+constexpr int64_t kMeTC2Floats = (int64_t)MET * MEC1 * MECOR;              // 2 x 108 chunks
+constexpr int64_t kMeTF2Floats = (int64_t)MET * MEF1 * MEFLO;              // 36 chunks
+constexpr int64_t kMeTCvAt = 0, kMeTC2At = kMeTCvAt + kMeTCvFloats, kMeTF2At = kMeTC2At + kMeTC2Floats;
+constexpr int64_t kMePackTFloats = kMeTF2At + kMeTF2Floats;
+static_assert((MET * MEOUT / MEKC) % MEFL == 0 && (MET * MECOR / MEKC) % MEFL == 0 && (MET * MEFLO / MEKC) % MEFL == 0,
+              "whole chains of the forward's length in every data gradient");
+// bias partials: per (batch item, 64-pixel block) one sum per channel of go [128] | gc2 [192] | gf2 [64] | gf1 [128]
+constexpr int kMeGbGo = 0, kMeGbC2 = MEOUT, kMeGbF2 = MEOUT + MECOR, kMeGbF1 = MEOUT + MECOR + MEFLO;
+constexpr int MEGB = kMeGbF1 + MEF1;               // 512
+// the largest weight gradient (convc2's): floats of one slab's partial; the four gradients take turns in it
+constexpr int64_t kMeWPartFloats = (int64_t)MECOR * MEC1 * MET;
+
 }  // namespace ecorr

@@ -25,7 +25,7 @@ from .alt_corr import AlternateCorrBlock
 from .corr import CorrBlock
 from .flow import upsample_flow as hip_upsample_flow
 from .gru import sepconv_gru, sepconv_gru_train
-from .motion_enc import motion_encoder
+from .motion_enc import motion_encoder, motion_encoder_train
 from .utils import coords_grid
 
 
@@ -247,6 +247,15 @@ class ERAFT(nn.Module):
     CorrBlock.lookup_conv1x1_relu under fuse_motion_corr, else from the lookup and torch's convc1.  fp32 and
     forward-only: it composes with fuse_motion_corr, hip_upsample, hip_gru and alternate_corr, and raises ValueError
     with mixed_precision, differentiable_corr, train_motion_corr, train_alternate_corr or train_gru.
+    train_motion_encoder=True (keyword only) runs it as eraft_amd.motion_encoder_train instead: the same forward
+    launches (under torch.no_grad() the predictions are bitwise hip_motion_encoder=True's) with the HIP backward of
+    csrc/motion_enc_grad.hip, so a loss on the predictions trains convc2, convf1, convf2 and conv
+    and everything in front of them through native kernels.  Every iteration gets a fresh x = cat([inp, m]): writing
+    into one reused x would overwrite what the GRU's node saved for its backward.  It composes with
+    differentiable_corr, train_motion_corr, train_alternate_corr, train_gru, fuse_motion_corr, alternate_corr and
+    hip_upsample; hip_motion_encoder=True may be passed along and changes nothing (its own refusals apply only
+    without train_motion_encoder).  The kernels are fp32: train_motion_encoder=True with mixed_precision=True raises
+    ValueError, and so does hip_gru=True without train_gru=True (a forward-only GRU behind a differentiable encoder).
     The defaults keep the reference's call pattern exactly."""
 
     corr_levels = 4
@@ -255,10 +264,18 @@ class ERAFT(nn.Module):
     def __init__(self, config, n_first_channels, fuse_motion_corr=False, hip_upsample=False,
                  differentiable_corr=False, train_motion_corr=False, mixed_precision=False,
                  amp_dtype=torch.float16, _native_half_lookup=True, *, alternate_corr=False,
-                 train_alternate_corr=False, hip_gru=False, train_gru=False, hip_motion_encoder=False):
+                 train_alternate_corr=False, hip_gru=False, train_gru=False, hip_motion_encoder=False,
+                 train_motion_encoder=False):
         super().__init__()
-        if hip_motion_encoder and (mixed_precision or differentiable_corr or train_motion_corr or
-                                   train_alternate_corr or train_gru):
+        if train_motion_encoder and mixed_precision:
+            raise ValueError("train_motion_encoder=True cannot be combined with mixed_precision: the HIP motion "
+                             "encoder and its backward are fp32")
+        if train_motion_encoder and hip_gru and not train_gru:
+            raise ValueError("train_motion_encoder=True cannot be combined with hip_gru=True unless train_gru=True: "
+                             "the HIP SepConvGRU alone is forward-only, so no gradient would reach the encoder")
+        self.train_motion_encoder = bool(train_motion_encoder)
+        if hip_motion_encoder and not train_motion_encoder and (mixed_precision or differentiable_corr or
+                                                                train_motion_corr or train_alternate_corr or train_gru):
             raise ValueError("hip_motion_encoder=True cannot be combined with mixed_precision, differentiable_corr, "
                              "train_motion_corr, train_alternate_corr or train_gru: the HIP motion encoder is fp32 "
                              "and forward-only")
@@ -364,19 +381,24 @@ class ERAFT(nn.Module):
         if flow_init is not None:
             coords1 = coords1 + flow_init
         predictions = []
-        if self.hip_motion_encoder:   # the GRU's input, assembled in place: inp once, the motion features per iteration
+        # the GRU's input, assembled in place: inp once, the motion features per iteration
+        if self.hip_motion_encoder and not self.train_motion_encoder:
             x = torch.empty((inp.shape[0], self.context_dim + 128) + tuple(inp.shape[2:]), dtype=torch.float32,
                             device=inp.device)
             x[:, :self.context_dim].copy_(inp)
         for _ in range(iters):
             coords1 = coords1.detach()
-            if self.hip_motion_encoder:   # fp32, no autocast: the constructor refuses mixed_precision
+            if self.hip_motion_encoder or self.train_motion_encoder:   # fp32, no autocast: mixed_precision is refused
                 enc = self.update_block.encoder
                 if self.fuse_motion_corr:
                     c1 = corr_fn.lookup_conv1x1_relu(coords1, enc.convc1.weight, enc.convc1.bias)
                 else:
                     c1 = F.relu(enc.convc1(corr_fn(coords1)))
-                motion_encoder(coords1 - coords0, c1.contiguous(), enc, out=x[:, self.context_dim:])
+                if self.train_motion_encoder:   # a fresh x: the GRU's node keeps the previous iteration's
+                    m = motion_encoder_train(coords1 - coords0, c1.contiguous(), enc)
+                    x = torch.cat([inp, m], 1)
+                else:
+                    motion_encoder(coords1 - coords0, c1.contiguous(), enc, out=x[:, self.context_dim:])
                 net, up_mask, delta = self.update_block(net, None, None, None, x=x)
             else:
                 if self.fuse_motion_corr:

@@ -580,7 +580,7 @@ int ecorr_sepconv_gru_backward(const float* h, const float* x, const float* grad
  * both contiguous fp32 and only read.  out: batch item b is float[128][H][W] at out + b * out_batch_stride (in
  * floats, >= 128 * H * W), so out may be the upper half of the GRU's x float[B][256][H][W] (out = x + 128 * H * W,
  * out_batch_stride = 256 * H * W) and neither concatenation runs.  H = 1 and W = 1 are valid (every off-centre
- * tap is then padding).  Forward only.
+ * tap is then padding).  Forward only (the gradients: ecorr_motion_encoder_backward).
  * Arithmetic: the three 3x3 convolutions run on the fp32 matrix instruction (exact fp32 operands, fp32
  * accumulation in chains of 192 products -- 12 chains for convc2 and conv, 6 for convf2 -- that are then summed),
  * convf1 as one k-ordered fmaf chain of 98 products; the bias is added last; relu is v < 0 ? 0 : v: within 1e-5 of
@@ -610,6 +610,57 @@ int ecorr_motion_encoder_pack(const float* const weight[4], const float* const b
 int ecorr_motion_encoder_workspace_size(int B, int H, int W, int64_t* bytes);
 int ecorr_motion_encoder(const float* c1, const float* flow, int B, int H, int W, const void* packed,
                          float* out, int64_t out_batch_stride, void* workspace, void* stream);
+
+/* ---- Motion encoder backward (four entries added within ABI 17: purely additive, the version stays 17) ----
+ * The gradients of ecorr_motion_encoder (csrc/motion_enc_grad.hip), first order, fp32, the same geometry limits.
+ * Given c1, flow (the forward's inputs) and grad_out = dL/dout, batch item b float[128][H][W] at grad_out + b *
+ * grad_out_batch_stride (in floats, >= 128 * H * W: it may be the upper half of the GRU's grad_x), with
+ * relu'(y) v = (y <= 0 ? 0 : v) on the ReLU's output y (a NaN y passes v, an exact 0 gives 0):
+ *   go = relu'(o) grad_out[:126], [gcor; gflo] = conv^T(go), gc2 = relu'(cor) gcor, gf2 = relu'(flo) gflo,
+ *   grad_c1 = convc2^T(gc2), gf1 = relu'(f1) convf2^T(gf2), grad_flow = convf1^T(gf1) + grad_out[126:128],
+ *   grad_weight[o][c][ky][kx] = sum over batch items and pixels p of gpre[o][p] in[c][p + (ky, kx) - reach] (valid
+ *   shifted pixels only), grad_bias[o] = the sum of gpre[o][p]; (gpre, in) = (go, [cor, flo]) for conv, (gc2, c1) for
+ *   convc2, (gf2, f1) for convf2, (gf1, flow) for convf1.
+ * Nothing but c1 and flow is kept from the forward: the call recomputes f1, cor and flo with the forward's kernels,
+ * so `packed` (ecorr_motion_encoder_pack) is needed too; conv's recompute writes go directly.
+ * Outputs: grad_c1 float[B][256][H][W], grad_flow float[B][2][H][W], each may be NULL (not wanted; a NULL grad_flow
+ * skips convf1's data gradient); grad_weight[i] and grad_bias[i] in the shapes and the order of
+ * ecorr_motion_encoder_pack (convc2 convf1 convf2 conv; host arrays of four device pointers), both arrays NULL (a
+ * frozen encoder: every weight GEMM and bias pass is skipped) or both complete.  Every element of a wanted output is
+ * overwritten.
+ * Arithmetic: the fp32 matrix instruction; the three 3x3 data gradients in chains of 192 products that are then
+ * summed (6 chains for conv^T, 9 for convc2^T, 3 for convf2^T); convf1^T on the VALU, per output one chain of 49
+ * products per f1 channel, the channels added in ascending order in four groups of 32, the groups in ascending
+ * order, grad_out's flow channels last; weight gradients in chains of at most 1024 pixels, summed per slab and then
+ * over the slabs in ascending order, a slab being a run of pixels of one batch item whose length depends on B, H and
+ * W alone; bias gradients as sums of 64 pixels added in ascending order.  No atomics: bitwise reproducible, and a
+ * batch item's grad_c1 and grad_flow do not depend on B.
+ * Transposed pack: ecorr_motion_encoder_backward_packed_size bytes = 4 * 9 * (256 * 128 + 256 * 192 + 128 * 64) =
+ * 3244032 (conv^T with its 126 reduction rows padded to 128, convc2^T, convf2^T; convf1 has none), 16-byte aligned,
+ * written once per weight set by ecorr_motion_encoder_backward_pack (one launch).
+ * Workspace: ecorr_motion_encoder_backward_workspace_size bytes, 16-byte aligned, no initialisation needed, contents
+ * undefined afterwards.  With n = B * H * W * 4 bytes and P = H * W:
+ *   896 * n                                      cor 192, f1 128, flo 64 | go 128 | gc2 192, gf2 64 | gf1 128
+ *   + align256(B * ceil(P / 64) * 512 * 4)       bias partials
+ *   + B * nsl * 9 * 192 * 256 * 4                weight slab partials (the largest gradient's; the four take turns)
+ * where cap = 1024, doubled while cap < P and B * ceil(P / cap) > 64; slab = ceil(ceil(P / ceil(P / cap)) / 32) * 32;
+ * nsl = ceil(P / slab); align256 rounds up to a multiple of 256 (the slab rule of ecorr_sepconv_gru_backward).
+ * ecorr_motion_encoder_backward: stream-ordered launches on `stream`, no host synchronisation, no allocation.
+ * Errors (before any GPU call), all ECORR_EINVAL: those of ecorr_motion_encoder (geometry: B, H or W < 1, B > 65535,
+ * H * W > 2097151; null c1, flow, packed, workspace; misaligned packed or workspace), a null grad_out or packed_t, a
+ * misaligned packed_t, grad_out_batch_stride < 128 * H * W (or beyond 2^40), all of grad_c1, grad_flow and
+ * grad_weight NULL, exactly one of grad_weight and grad_bias NULL, a NULL entry in either array, an output
+ * overlapping c1, flow, grad_out's whole strided extent ((B - 1) * grad_out_batch_stride + 128 * H * W floats), a
+ * pack, the workspace or another output, and the workspace overlapping c1, flow, that extent or a pack. */
+int ecorr_motion_encoder_backward_packed_size(int64_t* bytes);
+int ecorr_motion_encoder_backward_pack(const float* const weight[4], void* packed_t, void* stream);
+int ecorr_motion_encoder_backward_workspace_size(int B, int H, int W, int64_t* bytes);
+int ecorr_motion_encoder_backward(const float* c1, const float* flow, const float* grad_out,
+                                  int64_t grad_out_batch_stride, int B, int H, int W,
+                                  const void* packed, const void* packed_t,
+                                  float* grad_c1, float* grad_flow,
+                                  float* const grad_weight[4], float* const grad_bias[4],
+                                  void* workspace, void* stream);
 
 /* Tile shape of the pyramid storage (ECORR_TILE_H, ECORR_TILE_W). */
 int ecorr_pyramid_tile(int* tile_h, int* tile_w);
