@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from grad_slab_rule import assert_slab_shapes, slab_rule
 
 NAMES = ("ecorr_sepconv_gru_backward_packed_size", "ecorr_sepconv_gru_backward_pack",
          "ecorr_sepconv_gru_backward_workspace_size", "ecorr_sepconv_gru_backward")
@@ -62,11 +63,7 @@ def workspace_formula(B, H, W):
     """include/ecorr.h: 13 tensors of h's size, the bias partials and the weight slab partials."""
     P = H * W
     n = B * HID * P * 4
-    cap = 1024
-    while cap < P and B * -(-P // cap) > 64:
-        cap *= 2
-    slab = -(-(-(-P // -(-P // cap))) // 32) * 32
-    nsl = -(-P // slab)
+    _, nsl, _, _ = slab_rule(B, P)
     bias = (B * -(-P // 64) * 384 * 4 + 255) // 256 * 256
     return 13 * n + bias + B * nsl * 5 * 256 * 384 * 4
 
@@ -103,6 +100,19 @@ def test_sizes(ea):
                     (2, 1, 699051), (1, 46341, 46341)):
         assert L.ecorr_sepconv_gru_backward_workspace_size(B, HID, INP, H, W, ctypes.byref(n)) == E, (B, H, W)
     assert ws(1, 1, 1398101) == workspace_formula(1, 1, 1398101)
+
+
+def test_slab_shapes(ea):
+    """grad_slab_rule's table of the doubled cap and the second chain holds under the rule, and the library sizes
+    its workspace by that geometry: 33 and 44 slabs of partials."""
+    from eraft_amd import _lib
+    assert_slab_shapes()
+    for (B, H, W), slabs in (((33, 25, 41), 33), ((22, 33, 63), 44)):
+        m = ctypes.c_int64(-1)
+        assert ea.lib().ecorr_sepconv_gru_backward_workspace_size(B, HID, INP, H, W, ctypes.byref(m)) == _lib.ECORR_OK
+        assert m.value == workspace_formula(B, H, W), (B, H, W)
+        assert (m.value - 13 * B * HID * H * W * 4 - (B * -(-H * W // 64) * 384 * 4 + 255) // 256 * 256
+                == slabs * 5 * 256 * 384 * 4), (B, H, W)
 
 
 def test_validation_before_launch(ea):

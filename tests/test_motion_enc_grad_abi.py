@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from grad_slab_rule import assert_slab_shapes, slab_rule
 
 NAMES = ("ecorr_motion_encoder_backward_packed_size", "ecorr_motion_encoder_backward_pack",
          "ecorr_motion_encoder_backward_workspace_size", "ecorr_motion_encoder_backward")
@@ -66,11 +67,7 @@ def workspace_formula(B, H, W):
     """include/ecorr.h: 896 channels of [B][.][H W], the bias partials and the weight slab partials."""
     P = H * W
     n = B * P * 4
-    cap = 1024
-    while cap < P and B * -(-P // cap) > 64:
-        cap *= 2
-    slab = -(-(-(-P // -(-P // cap))) // 32) * 32
-    nsl = -(-P // slab)
+    _, nsl, _, _ = slab_rule(B, P)
     bias = (B * -(-P // 64) * 512 * 4 + 255) // 256 * 256
     return 896 * n + bias + B * nsl * 9 * 192 * 256 * 4
 
@@ -107,6 +104,19 @@ def test_sizes(ea):
     assert ws(1, 1, HW_MAX) == workspace_formula(1, 1, HW_MAX)
     assert ws(1, HW_MAX, 1) == workspace_formula(1, HW_MAX, 1)
     assert ws(65535, 1, HW_MAX) == workspace_formula(65535, 1, HW_MAX)
+
+
+def test_slab_shapes(ea):
+    """grad_slab_rule's table of the doubled cap and the second chain holds under the rule, and the library sizes
+    its workspace by that geometry: 33 and 44 slabs of partials."""
+    from eraft_amd import _lib
+    assert_slab_shapes()
+    for (B, H, W), slabs in (((33, 25, 41), 33), ((22, 33, 63), 44)):
+        m = ctypes.c_int64(-1)
+        assert ea.lib().ecorr_motion_encoder_backward_workspace_size(B, H, W, ctypes.byref(m)) == _lib.ECORR_OK
+        assert m.value == workspace_formula(B, H, W), (B, H, W)
+        assert (m.value - 896 * B * H * W * 4 - (B * -(-H * W // 64) * 512 * 4 + 255) // 256 * 256
+                == slabs * 9 * 192 * 256 * 4), (B, H, W)
 
 
 def test_validation_before_launch(ea):

@@ -12,7 +12,12 @@ Bars:
       for two independent fp32 roundings of the same sums; a wrong tap, border or slab is off by orders of magnitude.
 Shapes: test_motion_enc_gpu.SHAPES (H or W of 1, sizes shorter than every tap reach, 65 and 129 pixels, three batch
 items crossing row ends) and (2, 40, 50): 2000 pixels per item are two weight-gradient slabs of 1024 and 976 pixels,
-four in all with ragged last ones.
+four in all with ragged last ones.  None of these doubles the slab cap or runs a second chain in menc_wgrad_kernel;
+grad_slab_rule.SLAB_SHAPES do, and there the normal set is not used: with 17-23 million ReLU units per case a unit
+whose pre-activation lies within fp32 rounding of zero flips its mask (fp32 ATen on the CPU is itself 0.1 normwise from
+fp64 in grad_c1 and 0.028 in the weights at (22, 33, 63)), so a tolerance would flake or prove nothing.  They run on
+the integer-exact set of tests/menc_exact.py instead, where the forward and all ten gradients must equal the fp64
+reference cast to fp32 bit for bit (tests/test_menc_exact_ref.py shows fp32 ATen doing so on the CPU).
 """
 import copy
 import ctypes
@@ -22,8 +27,10 @@ import numpy as np
 import pytest
 import torch
 
+import menc_exact
 import prng
 from gpu_guard import Workspace, check_guarded, guarded, mismatch
+from grad_slab_rule import SLAB_GEOMETRY, SLAB_SHAPES, assert_single_chain, assert_slab_shapes, slab_rule, slabs_of
 from graph_capture import replay_matches_eager
 from test_motion_enc_gpu import SHAPES, cpu_module, gpu_module, make_inputs
 
@@ -257,6 +264,101 @@ def test_guards_and_raw_abi(shape):
             got = check_guarded(buf, f"motion_encoder backward {name}")
             assert np.isfinite(got).all(), name
             same(got, w, f"{name}: raw ABI (workspace of {fill:#x}, stride {stride}) against motion_encoder_train")
+
+
+EXACT_SHAPES = SLAB_SHAPES + [(3, 9, 15), (2, 40, 50)]
+
+
+def test_slab_geometry():
+    """SLAB_SHAPES have the doubled cap and the second chain the table states, the library sizes its partials by
+    that slab count, and no shape of GRAD_SHAPES reaches either branch."""
+    assert_slab_shapes()
+    assert_single_chain(GRAD_SHAPES)
+    for B, H, W in SLAB_SHAPES:
+        cap, nsl, slab, chains = slab_rule(B, H * W)
+        assert (cap, nsl, slab, slabs_of(H * W, nsl, slab)) == SLAB_GEOMETRY[(B, H, W)] and chains == 2
+        bias = (B * -(-H * W // 64) * 512 * 4 + 255) // 256 * 256
+        assert workspace_bytes(B, H, W) == 896 * B * H * W * 4 + bias + B * nsl * 9 * 192 * 256 * 4
+
+
+def exact_mod():
+    """A trainable copy of the GPU module holding the exact set's ternary weights."""
+    return menc_exact.exact_module(gpu_module()).requires_grad_(True)
+
+
+def exact_want(ref):
+    """The fp64 reference's ten gradients and forward output cast to fp32: every value is an integer below 2^24."""
+    return [g.astype(np.float32) for g in ref.grads], ref.out.astype(np.float32)
+
+
+@pytest.mark.parametrize("shape", EXACT_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_exact_set_bit_for_bit(shape):
+    """On the integer-exact set motion_encoder_train's forward and ten gradients, and motion_encoder's forward, are
+    the fp64 reference's bits: any tile, slab, chain or tap error changes an integer."""
+    import eraft_amd
+    ref = menc_exact.reference(shape)
+    assert ref.worst < menc_exact.LIMIT
+    want, fwd = exact_want(ref)
+    mod = exact_mod()
+    got, out = ours(ref.flow, ref.c1, ref.go, mod)
+    d = mismatch(out.cpu().numpy(), fwd)
+    assert d is None, f"motion_encoder_train forward: {d}"
+    for name, g, w in zip(NAMES, got, want):
+        assert g.shape == w.shape, name
+        assert np.any(w != 0), f"{name}: the reference gradient is identically zero"
+        same(g, w, f"{name} against the fp64 reference")
+    with torch.no_grad():
+        plain = eraft_amd.motion_encoder(ref.flow.cuda(), ref.c1.cuda(), mod)
+    d = mismatch(plain.cpu().numpy(), fwd)
+    assert d is None, f"motion_encoder forward: {d}"
+
+
+def test_exact_set_raw_abi_doubled_cap():
+    """(33, 25, 41) through the raw entry: all 10 outputs between guard bands and a workspace of exactly the reported
+    size between guards, prefilled with 0xff bytes.  The guards stay, every element is written, and the bits are the
+    fp64 reference's (so the Python path's)."""
+    shape = SLAB_SHAPES[0]
+    B, H, W = shape
+    assert slab_rule(B, H * W)[3] == 2
+    ref = menc_exact.reference(shape)
+    want, _ = exact_want(ref)
+    fd, cd, god = ref.flow.cuda(), ref.c1.cuda(), ref.go.cuda()
+    packs = raw_packs(exact_mod())
+    bufs = [guarded(n) for n in out_sizes(B, H, W)]
+    ws = Workspace(workspace_bytes(B, H, W), 0xff)
+    raw_backward(fd, cd, god.data_ptr(), OUT * H * W, packs, [b[1] for b in bufs], ws.ptr)
+    torch.cuda.synchronize()
+    ws.check("motion_encoder backward workspace")
+    for name, (buf, _), w in zip(NAMES, bufs, want):
+        got = check_guarded(buf, f"motion_encoder backward {name}")
+        same(got, w, f"{name}: raw ABI on the exact set against the fp64 reference")
+
+
+def test_strided_grad_out_from_cat():
+    """x = cat([inp, m], 1) hands m's node the upper half of x's gradient as a view of batch stride 256 H W: at B > 1
+    _MencFn.backward reads it in place.  The hook records that stride -- a contiguous tensor here would mean the
+    in-place branch never runs under this torch -- and all ten gradients are the contiguous call's bits."""
+    import eraft_amd
+    shape = (3, 9, 15)
+    B, H, W = shape
+    flow, c1, _, _, _ = case(shape)
+    gx = torch.from_numpy(prng.normal(811, (B, 2 * OUT, H, W)))
+    inp = torch.from_numpy(prng.normal(812, (B, OUT, H, W))).cuda().requires_grad_(True)
+    mod = train_mod()
+    fd, cd = flow.cuda().requires_grad_(True), c1.cuda().requires_grad_(True)
+    m = eraft_amd.motion_encoder_train(fd, cd, mod)
+    seen = []
+    m.register_hook(lambda g: seen.append((tuple(g.shape), tuple(g.stride()), g.dtype)))
+    x = torch.cat([inp, m], 1)
+    (x * gx.cuda()).sum().backward()
+    torch.cuda.synchronize()
+    assert seen == [((B, OUT, H, W), (2 * OUT * H * W, H * W, W, 1), torch.float32)], \
+        f"autograd delivered {seen}: not the upper half of grad_x in place, the no-copy branch did not run"
+    got = [fd.grad, cd.grad] + [getattr(mod, c).weight.grad for c in CONVS] + [getattr(mod, c).bias.grad for c in CONVS]
+    same(inp.grad.cpu().numpy(), gx[:, :OUT].numpy(), "inp.grad")
+    want, _ = ours(flow, c1, gx[:, OUT:].contiguous(), train_mod())
+    for name, g, w in zip(NAMES, got, want):
+        same(g.cpu().numpy(), w, f"{name}: strided grad_out against the contiguous call")
 
 
 def test_two_calls_same_bits_and_batch_independence():
